@@ -8,7 +8,11 @@ fly, resident in HBM when the timed kernels run). Whole-job value is the
 aggregate over all ranks (one process per GPU; sets shard across ranks with
 no data-path collective: weak scaling).
 
-Emits ONE JSON line from rank 0, including:
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line
+from rank 0 (value, ms_per_step, the in-run kernel-time splits and the
+algorithmic roofline figure). --dump-outputs DIR additionally writes what the
+last timed step returned to its caller (per-set consensus) as DIR/<name>.npy.
+Everything that takes runs of its own is behind --full, which adds:
   roofline:     dominant kernel (cg_global_mw_kernel) algorithmic HBM bytes/s
                 from HIP events on the library streams (6 B per DP cell at
                 int16: 3 planes H/E1/E2 written once; F planes recomputed at
@@ -73,23 +77,109 @@ def gen_sets(rng, n_sets, depth, qlen, p_sub=0.045, p_del=0.03, p_ins=0.025, alp
     return sets
 
 
-def build_batch_args(lib, sets):
-    n_sets = len(sets)
-    NSeqs = (ctypes.c_int * n_sets)(*[len(s) for s in sets])
-    seq_len_arrays = []
-    seq_ptr_arrays = []
-    keepalive = []
-    for s in sets:
-        lens = (ctypes.c_int * len(s))(*[len(r) for r in s])
-        seq_len_arrays.append(lens)
-        bufs = [ctypes.create_string_buffer(r, len(r)) for r in s]
-        keepalive.append(bufs)
-        ptrs = (ctypes.POINTER(ctypes.c_uint8) * len(s))(
-            *[ctypes.cast(b, ctypes.POINTER(ctypes.c_uint8)) for b in bufs])
-        seq_ptr_arrays.append(ptrs)
-    LensTop = (ctypes.POINTER(ctypes.c_int) * n_sets)(*seq_len_arrays)
-    SeqsTop = (ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)) * n_sets)(*seq_ptr_arrays)
-    return NSeqs, LensTop, SeqsTop, (seq_len_arrays, seq_ptr_arrays, keepalive)
+# Sets per generator stream. Fixed, so a step's inputs depend only on
+# (rank, step index, arguments) and never on how many workers generate them.
+GEN_CHUNK = 25
+
+
+def _gen_chunk(job):
+    """One chunk of a step's read sets from its own seeded stream, flattened
+    for cheap transport: (all reads back to back, int32 length per read)."""
+    import numpy as np
+    seed, n, depth, qlen, alphabet = job
+    sets = gen_sets(np.random.default_rng(seed), n, depth, qlen, alphabet=alphabet)
+    reads = [r for s in sets for r in s]
+    return b"".join(reads), np.array([len(r) for r in reads], dtype=np.int32)
+
+
+def gen_step_chunks(pool, rank, step_idx, n_sets, depth, qlen, alphabet):
+    """Inputs of one step: a list of _gen_chunk results, identical from run
+    to run for the same arguments. With a pool, returns the pending result
+    (.get() yields the list), so that several steps can be in flight."""
+    jobs = [([4242 + 1000 * rank, step_idx, c], min(GEN_CHUNK, n_sets - c * GEN_CHUNK),
+             depth, qlen, alphabet)
+            for c in range((n_sets + GEN_CHUNK - 1) // GEN_CHUNK)]
+    if pool is None:
+        return [_gen_chunk(j) for j in jobs]
+    return pool.map_async(_gen_chunk, jobs, chunksize=1)
+
+
+def gen_workers(n_sets):
+    """Generator processes for this rank: the CPUs it may run on, shared among
+    the ranks of this node, 16 at the most."""
+    try:
+        ncpu = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        ncpu = os.cpu_count() or 1
+    per_rank = min(16, ncpu) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1")))
+    return max(1, min(per_rank, (n_sets + GEN_CHUNK - 1) // GEN_CHUNK))
+
+
+def build_batch_args_flat(chunks, depth):
+    """abpoa_amd_msa_batch argument trees over the chunks' flat read buffers
+    (every set holds `depth` reads): pointer tables are computed by address
+    arithmetic instead of one ctypes object per read."""
+    import numpy as np
+    lens = np.concatenate([c[1] for c in chunks])
+    n_sets = len(lens) // depth
+    assert n_sets * depth == len(lens)
+    ptrs = np.empty(len(lens), dtype=np.uint64)
+    bufs = []
+    at = 0
+    for data, clens in chunks:
+        buf = np.frombuffer(data, dtype=np.uint8)
+        assert int(clens.sum()) == len(buf)
+        off = np.zeros(len(clens), dtype=np.uint64)
+        off[1:] = np.cumsum(clens[:-1], dtype=np.int64)
+        ptrs[at:at + len(clens)] = np.uint64(buf.ctypes.data) + off
+        at += len(clens)
+        bufs.append(buf)
+    nseqs = np.full(n_sets, depth, dtype=np.int32)
+    step = np.arange(n_sets, dtype=np.uint64) * np.uint64(depth)
+    lens_top = np.uint64(lens.ctypes.data) + step * np.uint64(4)
+    seqs_top = np.uint64(ptrs.ctypes.data) + step * np.uint64(8)
+    PI = ctypes.POINTER(ctypes.c_int)
+    PB = ctypes.POINTER(ctypes.c_uint8)
+    return (ctypes.cast(nseqs.ctypes.data, PI),
+            ctypes.cast(lens_top.ctypes.data, ctypes.POINTER(PI)),
+            ctypes.cast(seqs_top.ctypes.data, ctypes.POINTER(ctypes.POINTER(PB))),
+            (chunks, bufs, lens, ptrs, nseqs, lens_top, seqs_top))
+
+
+DUMP_BUDGET = 60 * 1000 * 1000  # bytes of .npy payload, all files together
+
+
+def _dump_rows(n_rows, row_bytes, budget):
+    """Row indices to dump: all of them, or a fixed seeded sample that fits."""
+    import numpy as np
+    k = max(1, min(n_rows, budget // max(1, row_bytes)))
+    if k == n_rows:
+        return np.arange(n_rows)
+    return np.sort(np.random.default_rng(20240229).choice(n_rows, size=k, replace=False))
+
+
+def dump_outputs(out_dir, results):
+    """Write what the last timed step handed to its caller: per set, the
+    consensus length, bases (codes 0..m-1) and per-base coverage. Rows are
+    padded with -1 to the longest consensus; cons_base/cons_cov hold the sets
+    listed in <name>_sets.npy (all of them while they fit the size budget)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(results)
+    missing = [i for i, r in enumerate(results) if r is None]
+    assert not missing, "batch driver returned no consensus for sets %r" % missing[:10]
+    cons_len = np.array([len(r[0]) for r in results], dtype=np.float64)
+    width = max(1, int(cons_len.max()) if n else 1)
+    np.save(os.path.join(out_dir, "cons_len.npy"), cons_len)
+    budget = DUMP_BUDGET - cons_len.nbytes
+    for name, col, share in (("cons_base", 0, 0.7), ("cons_cov", 1, 0.3)):
+        rows = _dump_rows(n, width * 4 + 8, int(budget * share))
+        arr = np.full((len(rows), width), -1.0, dtype=np.float32)
+        for k, s in enumerate(rows):
+            v = results[s][col]
+            arr[k, :len(v)] = v
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        np.save(os.path.join(out_dir, name + "_sets.npy"), rows.astype(np.float64))
 
 
 class Para(ctypes.Structure):
@@ -143,14 +233,6 @@ def native_setup():
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
     lib.abpoa_amd_msa_batch.restype = ctypes.c_int
     return lib
-
-
-def run_step(lib, para, sets, n_threads):
-    NSeqs, LensTop, SeqsTop, keep = build_batch_args(lib, sets)
-    rc = lib.abpoa_amd_msa_batch(para, len(sets), NSeqs, LensTop, SeqsTop,
-                                 None, None, n_threads)
-    assert rc == 0
-    del keep
 
 
 def _cpu_model():
@@ -321,6 +403,13 @@ def main():
                     help="exercise the distributed harness without a GPU (CPU tests)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cg",
                     help="BASELINE config variant; default = configs[1] (the driver's contract)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-set consensus (length, bases, "
+                         "coverage) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: counter-measured "
+                         "roofline traffic (rocprofv3 --pmc probe passes) and the CPU "
+                         "baseline (reference binary)")
     args = ap.parse_args()
     if args.workload == "aa":
         # configs[3]: 30 reads x 2 kaa unless explicitly overridden
@@ -337,6 +426,32 @@ def main():
     # (hipStreamSynchronize at every batch end).
     if "HIP_VISIBLE_DEVICES" not in os.environ and "LOCAL_RANK" in os.environ:
         os.environ["HIP_VISIBLE_DEVICES"] = os.environ["LOCAL_RANK"]
+
+    # Pregenerate every step's input OUTSIDE the timed region (the metric is
+    # quoted with inputs resident; generation is not part of the hot path) and
+    # prebuild the argument trees so the timed loop only runs the native
+    # driver. Generation is spread over worker processes, which are gone
+    # before the native library loads or any rank rendezvous starts.
+    alphabet = 20 if args.workload == "aa" else 4
+    prepared = []
+    if not args.dry_run:
+        import multiprocessing
+        n_workers = gen_workers(args.sets_per_step)
+        pool = multiprocessing.get_context("fork").Pool(n_workers) if n_workers > 1 else None
+        try:
+            # all steps are queued at once, so no worker idles at a step's end
+            pending = [gen_step_chunks(pool, rank, step_idx, args.sets_per_step,
+                                       args.depth, args.qlen, alphabet)
+                       for step_idx in range(args.warmup + args.steps)]
+            for chunks in pending:
+                if pool is not None:
+                    chunks = chunks.get()
+                prepared.append(build_batch_args_flat(chunks, args.depth))
+        finally:
+            if pool is not None:
+                pool.close()
+                pool.join()
+
     dist = None
     if world > 1 or os.environ.get("MASTER_ADDR"):
         import torch.distributed as tdist
@@ -352,26 +467,34 @@ def main():
         para = make_para(lib, args.workload)
         import abpoa_amd
 
-    rng = np.random.default_rng(4242 + 1000 * rank)
-    alphabet = 20 if args.workload == "aa" else 4
+    # --dump-outputs: the last timed step hands its consensus to a callback,
+    # as any caller of the batch driver would receive it (the driver runs the
+    # callbacks serially on the calling thread after the whole batch is done).
+    dumped = [None] * args.sets_per_step
+    dump_cb = None
+    if args.dump_outputs and not args.dry_run and rank == 0:
+        from abpoa_amd import CONS_CB
 
-    # Pregenerate every step's input OUTSIDE the timed region (the metric is
-    # quoted with inputs resident; generation is not part of the hot path) and
-    # prebuild the ctypes argument trees so the timed loop only runs the
-    # native driver.
-    prepared = []
-    if not args.dry_run:
-        for _ in range(args.warmup + args.steps):
-            sets = gen_sets(rng, args.sets_per_step, args.depth, args.qlen, alphabet=alphabet)
-            prepared.append(build_batch_args(lib, sets))
+        @CONS_CB
+        def dump_cb(idx, cons_p, _user):
+            c = cons_p.contents
+            ln = c.cons_len[0] if c.n_cons > 0 else 0
+            base = np.frombuffer(ctypes.string_at(c.cons_base[0], ln), dtype=np.uint8) \
+                if ln else np.zeros(0, np.uint8)
+            cov = np.frombuffer(ctypes.string_at(c.cons_cov[0], 4 * ln), dtype=np.int32) \
+                if ln and c.cons_cov and c.cons_cov[0] else np.zeros(0, np.int32)
+            dumped[idx] = (base, cov)
 
     def one_step(step_idx):
         if args.dry_run:
             time.sleep(0.01)
             return
         NSeqs, LensTop, SeqsTop, _keep = prepared[step_idx]
+        cb = None
+        if dump_cb is not None and step_idx == args.warmup + args.steps - 1:
+            cb = ctypes.cast(dump_cb, ctypes.c_void_p)
         rc = lib.abpoa_amd_msa_batch(para, args.sets_per_step, NSeqs, LensTop,
-                                     SeqsTop, None, None, args.threads)
+                                     SeqsTop, cb, None, args.threads)
         assert rc == 0
 
     def barrier_sync():
@@ -416,6 +539,8 @@ def main():
             print(json.dumps(line), flush=True)
             return
         import abpoa_amd
+        if dump_cb is not None:
+            dump_outputs(args.dump_outputs, dumped)
         cells, kns, launches = abpoa_amd.get_stats()
         import ctypes as _ct
         _ab = _ct.c_uint64()
@@ -435,7 +560,7 @@ def main():
             dp_s = kns / 1e9; fold_s = 0.0; busy_s = None
         ach = alg_bytes / max(kns, 1)  # bytes/ns == GB/s (per summed DP event time)
         try:
-            traffic = traffic_probe(args) if world == 1 else None
+            traffic = traffic_probe(args) if args.full and world == 1 else None
         except Exception:
             traffic = None  # traffic is evidence, never a reason to fail the run
         tval = None
@@ -448,7 +573,7 @@ def main():
                     "traffic_note": ("PMC FETCH_SIZE(x2 gfx950 correction)+WRITE_SIZE per DP-kernel launch, "
                                      "separate --pmc passes on a %d-set probe, scaled by cells"
                                      % traffic["probe_sets"]) if traffic else None}
-        cpu = cpu_baseline_leg(args.depth, args.qlen) if world == 1 else None
+        cpu = cpu_baseline_leg(args.depth, args.qlen) if args.full and world == 1 else None
         wl_desc = WORKLOAD if args.workload == "cg" else (
             "%d synthetic sets x %d reads x %d bp, %s, 1 MI355X"
             % (args.sets_per_step, args.depth, args.qlen, WORKLOADS[args.workload][0]))

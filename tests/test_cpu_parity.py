@@ -11,7 +11,7 @@ import os
 import subprocess
 import pytest
 
-from conftest import GOLDEN, ROOT, REF_BIN, run_stdout
+from conftest import GOLDEN, ROOT, run_stdout
 
 CASES = [
     ("seq.fa", [], "expected_seq_cons.txt"),
@@ -104,14 +104,14 @@ def test_aa_mode_vs_reference(cputest_bin, oracle_env, ref_bin, tmp_path):
         assert got == ref
 
 
-def test_pog_dot_output(cputest_bin, oracle_env, tmp_path):
+def test_pog_dot_output(cputest_bin, oracle_env, ref_bin, tmp_path):
     """--out-pog DOT file is byte-identical to the reference's (the graphviz
     render step itself needs `dot`, absent here; both sides fail alike)."""
     import subprocess
     ref_png = tmp_path / "ref.png"
     amd_png = tmp_path / "amd.png"
     fa = os.path.join(GOLDEN, "seq.fa")
-    subprocess.run([REF_BIN, fa, "-g", str(ref_png)], stdout=subprocess.DEVNULL,
+    subprocess.run([ref_bin, fa, "-g", str(ref_png)], stdout=subprocess.DEVNULL,
                    stderr=subprocess.DEVNULL)
     subprocess.run([cputest_bin, fa, "-g", str(amd_png)], env=oracle_env,
                    stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
@@ -120,7 +120,7 @@ def test_pog_dot_output(cputest_bin, oracle_env, tmp_path):
     assert ref_dot == amd_dot
 
 
-def test_list_input_mode(cputest_bin, oracle_env, tmp_path):
+def test_list_input_mode(cputest_bin, oracle_env, ref_bin, tmp_path):
     """-l: input file is a list of FASTA paths, one MSA per file with
     batch_index-numbered consensus headers (abpoa.c:152-161)."""
     lst = tmp_path / "list.txt"
@@ -133,13 +133,13 @@ def test_list_input_mode(cputest_bin, oracle_env, tmp_path):
         fas.append(str(fa))
     lst.write_text("".join(p + "\n" for p in fas))
     for opts in ([], ["-r1"]):
-        ref = subprocess.run([REF_BIN, "-l", str(lst)] + opts, stdout=subprocess.PIPE,
+        ref = subprocess.run([ref_bin, "-l", str(lst)] + opts, stdout=subprocess.PIPE,
                              stderr=subprocess.DEVNULL).stdout
         amd = run_stdout([cputest_bin, "-l", str(lst)] + opts, env=oracle_env)
         assert ref == amd
 
 
-def test_quality_weights_fastq(cputest_bin, oracle_env, tmp_path):
+def test_quality_weights_fastq(cputest_bin, oracle_env, ref_bin, tmp_path):
     """-Q: FASTQ qualities become per-base edge weights; weighted consensus,
     MSA, FASTQ output and weighted multi-consensus must match."""
     import random
@@ -158,7 +158,7 @@ def test_quality_weights_fastq(cputest_bin, oracle_env, tmp_path):
             qual = "".join(chr(33 + rng.randrange(5, 40)) for _ in s)
             f.write("@r%d\n%s\n+\n%s\n" % (i, s, qual))
     for opts in (["-Q"], ["-Q", "-r1"], ["-Q", "-d2"], ["-Q", "-r4"], ["-Q", "-a1"]):
-        ref = subprocess.run([REF_BIN, str(fq)] + opts, stdout=subprocess.PIPE,
+        ref = subprocess.run([ref_bin, str(fq)] + opts, stdout=subprocess.PIPE,
                              stderr=subprocess.DEVNULL).stdout
         amd = run_stdout([cputest_bin, str(fq)] + opts, env=oracle_env)
         assert ref == amd, "mismatch opts=%r" % (opts,)
