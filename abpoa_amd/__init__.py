@@ -59,11 +59,40 @@ class ConsT(ctypes.Structure):
 CONS_CB = ctypes.CFUNCTYPE(None, ctypes.c_int, ctypes.POINTER(ConsT), ctypes.c_void_p)
 
 
-def msa_batch_consensus(sets, n_threads=4, cons_algrm=None):
+def get_cons_stats():
+    """Consensus-stage counters of the batched driver since the last reset:
+    dict(device_sets, host_sets, fallback_sets, d2h_bytes, kernel_ns).
+    device_sets took the GPU consensus kernel; host_sets downloaded their graph
+    for the host pass (fallback_sets of them after a non-OK device status)."""
+    L = lib()
+    L.abpoa_amd_get_cons_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)] * 5
+    L.abpoa_amd_get_cons_stats.restype = None
+    v = [ctypes.c_uint64() for _ in range(5)]
+    L.abpoa_amd_get_cons_stats(*[ctypes.byref(x) for x in v])
+    keys = ("device_sets", "host_sets", "fallback_sets", "d2h_bytes", "kernel_ns")
+    return dict(zip(keys, (x.value for x in v)))
+
+
+def reset_cons_stats():
+    L = lib()
+    L.abpoa_amd_reset_cons_stats.restype = None
+    L.abpoa_amd_reset_cons_stats()
+
+
+_ACGT = "ACGTN-"
+
+
+def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1):
     """Run the batched GPU driver over `sets` (list of list of bytes, codes
-    0..3) and return each set's consensus as an ACGT string.
+    0..3) and return, per set, the full callback payload as a dict:
+      cons          list of consensus strings (one per cluster)
+      node_ids/cov/phred   per-cluster lists of ints, one entry per base
+      clu_n_seq     reads per cluster
+      clu_read_ids  per-cluster read-id lists
+      n_seq         reads in the set
     cons_algrm: None = library default (HB), "MF" = most-frequent (exercises
-    the per-edge read-id bitsets on the device-resident path)."""
+    the per-edge read-id bitsets on the device-resident path).
+    max_n_cons: 1 or 2 consensus sequences per set."""
     L = lib()
     L.abpoa_init_para.restype = ctypes.c_void_p
     L.abpoa_post_set_para.argtypes = [ctypes.c_void_p]
@@ -75,10 +104,15 @@ def msa_batch_consensus(sets, n_threads=4, cons_algrm=None):
         ctypes.POINTER(ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))),
         CONS_CB, ctypes.c_void_p, ctypes.c_int]
     para = L.abpoa_init_para()
-    if cons_algrm is not None:
+    if cons_algrm is not None or max_n_cons != 1:
         from .pyabpoa import ParaT, ABPOA_HB, ABPOA_MF
         p = ctypes.cast(para, ctypes.POINTER(ParaT)).contents
-        p.cons_algrm = {"HB": ABPOA_HB, "MF": ABPOA_MF}[cons_algrm.upper()]
+        if cons_algrm is not None:
+            p.cons_algrm = {"HB": ABPOA_HB, "MF": ABPOA_MF}[cons_algrm.upper()]
+        if max_n_cons != 1:
+            if max_n_cons < 1 or max_n_cons > 2:
+                raise ValueError("max_n_cons must be 1 or 2")
+            p.max_n_cons = max_n_cons
     L.abpoa_post_set_para(para)
 
     n_sets = len(sets)
@@ -96,18 +130,34 @@ def msa_batch_consensus(sets, n_threads=4, cons_algrm=None):
     SeqsTop = (ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)) * n_sets)(*ptrs_keep)
 
     out = [None] * n_sets
-    ACGT = "ACGTN-"
 
     @CONS_CB
     def cb(idx, cons_p, _user):
         c = cons_p.contents
-        seqs = []
+        r = {"n_seq": c.n_seq, "cons": [], "node_ids": [], "cov": [], "phred": [],
+             "clu_n_seq": [], "clu_read_ids": []}
         for ci in range(c.n_cons):
             ln = c.cons_len[ci]
-            seqs.append("".join(ACGT[c.cons_base[ci][j]] for j in range(ln)))
-        out[idx] = seqs[0] if len(seqs) == 1 else seqs
+            r["cons"].append("".join(_ACGT[b] for b in c.cons_base[ci][:ln]))
+            r["node_ids"].append(c.cons_node_ids[ci][:ln])
+            r["cov"].append(c.cons_cov[ci][:ln])
+            r["phred"].append(c.cons_phred_score[ci][:ln])
+            r["clu_n_seq"].append(c.clu_n_seq[ci])
+            r["clu_read_ids"].append(c.clu_read_ids[ci][:c.clu_n_seq[ci]])
+        out[idx] = r
 
     rc = L.abpoa_amd_msa_batch(para, n_sets, NSeqs, LensTop, SeqsTop, cb, None, n_threads)
     L.abpoa_free_para(para)
     assert rc == 0
+    return out
+
+
+def msa_batch_consensus(sets, n_threads=4, cons_algrm=None):
+    """Run the batched GPU driver over `sets` (list of list of bytes, codes
+    0..3) and return each set's consensus as an ACGT string (a list of
+    strings where a set yields several). See msa_batch_results."""
+    out = []
+    for r in msa_batch_results(sets, n_threads=n_threads, cons_algrm=cons_algrm):
+        seqs = r["cons"]
+        out.append(seqs[0] if len(seqs) == 1 else seqs)
     return out

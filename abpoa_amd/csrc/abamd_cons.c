@@ -584,6 +584,35 @@ static void heaviest_bundling(abpoa_graph_t *g, abpoa_para_t *abpt, int src_id, 
     free(max_out_id);
 }
 
+/* Assemble the result heaviest_bundling() produces for n_clu == 1 from an
+ * already-chosen consensus path (the device-resident batch driver computes
+ * ids/bases/coverage on the GPU and downloads only those). Phred is a pure
+ * function of (coverage, n_seq), so it is derived here with the same
+ * cons_phred_score — its n_cov > n_seq check included — once per distinct
+ * coverage value. `abc` must be cleared (as after cons_new/cons_clear). */
+void abamd_cons_from_path(abpoa_cons_t *abc, int n_seq, int cons_len, const int *ids,
+                          const uint8_t *bases, const int *cov) {
+    int i, j;
+    int *phred_of = (int*)abamd_malloc((size_t)(n_seq > 0 ? n_seq + 1 : 1) * sizeof(int));
+    for (i = 0; i <= n_seq; ++i) phred_of[i] = -1;
+    allocate_cons(abc, cons_len > 0 ? cons_len : 1, n_seq, 1);
+    abc->clu_n_seq[0] = abc->n_seq;
+    for (i = 0; i < abc->n_seq; ++i) abc->clu_read_ids[0][i] = i;
+    for (j = 0; j < cons_len; ++j) {
+        const int c = cov[j];
+        abc->cons_node_ids[0][j] = ids[j];
+        abc->cons_base[0][j] = bases[j];
+        abc->cons_cov[0][j] = c;
+        if (c < 0 || c > n_seq) abc->cons_phred_score[0][j] = cons_phred_score(c, n_seq);
+        else {
+            if (phred_of[c] < 0) phred_of[c] = cons_phred_score(c, n_seq);
+            abc->cons_phred_score[0][j] = phred_of[c];
+        }
+    }
+    abc->cons_len[0] = cons_len;
+    free(phred_of);
+}
+
 /* node msa rank = max over its aligned group (abpoa_output.c:136-144) */
 static int group_msa_rank(abpoa_graph_t *g, int id) {
     int k, rank = g->node_id_to_msa_rank[id];

@@ -22,6 +22,15 @@ typedef struct flat_graph_t {
     int *aln_id, *aln_next;                         /* [aln_cap] */
 } flat_graph_t;
 
+/* phased flat consensus (abamd_cons_core.inc): per-job status and the row
+ * count staged per step of the reverse sweep (= the device wave width) */
+enum {
+    ABAMD_CONS_OK = 0,
+    ABAMD_CONS_BAD_GRAPH = 1     /* no SRC->SINK walk through the chosen edges:
+                                    only a corrupt graph / topo order gives it */
+};
+#define ABAMD_CONS_CHUNK 64
+
 /* Device translation units (gpu_fold.hip) include this header for the
  * flat_graph_t layout only: the function bodies there are __device__ builds
  * of abamd_fold_core.inc, and host declarations of the same names would
@@ -57,7 +66,23 @@ int abamd_flat_hb_consensus(const flat_graph_t *fg, int n_seq,
                             int *cons_id, uint8_t *cons_base,
                             int *cons_cov, int *cons_phred);
 
+/* the same consensus in four phases over the fold's topological order
+ * (rows 0..n2i[SINK]); host build of the device kernel's body — call with
+ * lane 0 of 1. Workspaces: max_w/best/score/path n2i[SINK]+1 ints, stage
+ * 3*ABAMD_CONS_CHUNK ints; cons_id may alias path. Returns ABAMD_CONS_*. */
+int abamd_flat_cons_phased(const flat_graph_t *fg, const int *i2n, const int *n2i,
+                           int *max_w, int *best, int *score, int *path,
+                           int *cons_id, uint8_t *cons_base, int *cons_cov,
+                           int *stage, int *cons_len_out, int lane, int n_lanes);
+
 #ifdef ABPOA_AMD_H
+/* Build the single-cluster abpoa_cons_t the heaviest-bundle pass produces
+ * from a consensus path (abamd_cons.c): phred from coverage on the host,
+ * n_cons = 1, every read in cluster 0. `abc` must be cleared. */
+void abamd_cons_from_path(abpoa_cons_t *abc, int n_seq, int cons_len, const int *ids,
+                          const uint8_t *bases, const int *cov);
+/* free an abpoa_cons_t's arrays and zero it (abamd_graph.c) */
+void abamd_cons_clear(abpoa_cons_t *abc);
 /* Rebuild a pointer graph from a (host copy of a) flat graph and topo-sort
  * it — the device-resident batch driver's hand-off to the host consensus
  * path (abamd_graph.c). `ab` must be fresh. All node arrays are carved from

@@ -100,6 +100,8 @@ void abpoa_free(abpoa_t *ab) {
 }
 
 void abpoa_clean_msa_cons(abpoa_t *ab) { cons_clear(ab->abc); }
+/* same cleanup for a result that belongs to no abpoa_t (device consensus) */
+void abamd_cons_clear(abpoa_cons_t *abc) { cons_clear(abc); }
 
 /* ---------------- node / edge mutation ---------------- */
 

@@ -58,6 +58,30 @@ typedef struct {
 /* launcher (gpu_fold.hip); stream is a hipStream_t */
 void abamd_launch_fold_round(const abamd_fold_round_job_t *dev_jobs, int n_jobs, void *stream);
 
+/* ---- device consensus (gpu_fold.hip :: abamd_cons_kernel) ----
+ * One job = one read set's FINAL graph: single-cluster heaviest-bundle
+ * consensus in four phases (abamd_cons_core.inc :: abamd_flat_cons_phased)
+ * over the topological order the last fold left in i2n/n2i. The graph pools,
+ * i2n and n2i are only read; the workspaces are slab regions that are dead
+ * after the last fold. The host downloads `out` first, then cons_len entries
+ * of cons_id/cons_base/cons_cov. */
+typedef struct {
+    int32_t status;              /* ABAMD_CONS_* (abamd_fold_core.h) */
+    int32_t cons_len;
+} abamd_cons_out_t;
+
+typedef struct {
+    flat_graph_t g;              /* device ptrs; counters = host mirror */
+    const int *index_to_node_id, *node_id_to_index;
+    int *max_w, *best, *score;   /* row space, >= n_rows ints each */
+    int *cons_id;                /* also holds the row path before the gather */
+    uint8_t *cons_base;
+    int *cons_cov;
+    abamd_cons_out_t *out;
+} abamd_cons_job_t;
+
+void abamd_launch_cons(const abamd_cons_job_t *dev_jobs, int n_jobs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

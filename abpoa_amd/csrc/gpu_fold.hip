@@ -42,6 +42,10 @@ typedef uint64_t abpoa_cigar_t;
 #define ABAMD_FC_FAIL(msg) do { abort(); } while (0)
 #define ABAMD_FC_FAIL_RET(val, msg) do { abort(); } while (0)
 #include "abamd_fold_core.inc"
+/* consensus body: the phases synchronise the workgroup between them; the
+ * queue-based witness (double pow/log10 phred) is host-only */
+#define ABAMD_FC_BARRIER() __syncthreads()
+#define ABAMD_CONS_PHASED_ONLY
 #include "abamd_cons_core.inc"
 
 /* ------------------------------------------------------------------ */
@@ -477,30 +481,44 @@ void abamd_fold_round_kernel(abamd_fold_round_job_t *jobs, int n_jobs) {
 }
 
 
-/* Round-3 skeleton: per-set single-cluster consensus on device (compile-
- * checked; not wired — the resident driver still downloads graphs and runs
- * host consensus). One block per set, the twin-proven core on lane 0;
- * phred parity (double pow/log10 on device libm) must be validated on
- * hardware before wiring. */
-typedef struct {
-    flat_graph_t g;
-    int n_seq;
-    int *scratch, *score, *max_out;
-    int *cons_id; uint8_t *cons_base; int *cons_cov, *cons_phred;
-    int *cons_len_out;
-} abamd_cons_job_t;
+/* ------------------------------------------------------------------ */
+/* Device consensus kernel.                                            */
+/* ------------------------------------------------------------------ */
 
-extern "C" __global__ void abamd_cons_kernel(abamd_cons_job_t *jobs, int n_jobs) {
-    int j = blockIdx.x;
+/* Per-set single-cluster heaviest-bundle consensus on the set's final
+ * graph: one 64-lane workgroup per set runs the four phases of
+ * abamd_flat_cons_phased (abamd_cons_core.inc; the host twin runs the same
+ * body with one lane, tests/test_cons_twin): lane-parallel edge scan, serial
+ * reverse sweep over rows staged 64 at a time through LDS (phase-1 results
+ * in, scores + final choices out, both coalesced — per untied row the only
+ * dependent access left is the successor's score, which sits in the LDS
+ * window for in-chunk successors), bounded path walk, lane-parallel gather.
+ * No abort() and no unbounded loop: a graph that yields no SRC->SINK walk
+ * sets ABAMD_CONS_BAD_GRAPH for that job and the host falls back for that
+ * set alone. LDS: 3 x 64 ints = 768 B. Phred is derived on the host from
+ * the downloaded coverage. */
+extern "C" __global__ __launch_bounds__(FOLD_WAVE)
+void abamd_cons_kernel(const abamd_cons_job_t *jobs, int n_jobs) {
+    __shared__ int stage[3 * ABAMD_CONS_CHUNK];
+    const int j = blockIdx.x;
     if (j >= n_jobs) return;
-    abamd_cons_job_t *job = &jobs[j];
+    const abamd_cons_job_t *job = &jobs[j];
+    const flat_graph_t gl = job->g; /* by value: pool pointers in registers */
+    int cons_len = 0;
+    const int status = abamd_flat_cons_phased(&gl, job->index_to_node_id, job->node_id_to_index,
+                                              job->max_w, job->best, job->score,
+                                              job->cons_id /* row path */, job->cons_id,
+                                              job->cons_base, job->cons_cov,
+                                              stage, &cons_len, (int)threadIdx.x, FOLD_WAVE);
     if (threadIdx.x == 0) {
-        flat_graph_t gl = job->g;
-        *job->cons_len_out = abamd_flat_hb_consensus(&gl, job->n_seq,
-                                                     job->scratch, job->score, job->max_out,
-                                                     job->cons_id, job->cons_base,
-                                                     job->cons_cov, job->cons_phred);
+        job->out->status = status;
+        job->out->cons_len = cons_len;
     }
+}
+
+extern "C" void abamd_launch_cons(const abamd_cons_job_t *dev_jobs, int n_jobs, void *stream) {
+    hipLaunchKernelGGL(abamd_cons_kernel, dim3(n_jobs), dim3(FOLD_WAVE), 0,
+                       (hipStream_t)stream, dev_jobs, n_jobs);
 }
 
 extern "C" void abamd_launch_fold_round(const abamd_fold_round_job_t *dev_jobs,

@@ -37,6 +37,17 @@ int abamd_gpu_align_batch(abamd_batch_job_t *batch, int n_jobs) {
 }
 
 void abpoa_amd_get_stats2(uint64_t *alg_bytes) { if (alg_bytes) *alg_bytes = 0; }
+
+/* no device consensus in the CPU test build: the counters stay zero */
+void abpoa_amd_get_cons_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_t *fallback_sets,
+                              uint64_t *d2h_bytes, uint64_t *kernel_ns) {
+    if (device_sets) *device_sets = 0;
+    if (host_sets) *host_sets = 0;
+    if (fallback_sets) *fallback_sets = 0;
+    if (d2h_bytes) *d2h_bytes = 0;
+    if (kernel_ns) *kernel_ns = 0;
+}
+void abpoa_amd_reset_cons_stats(void) {}
 void abamd_timing_report(const char *tag) { (void)tag; }
 
 static abamd_batch_job_t *stub_slot_batch[8];

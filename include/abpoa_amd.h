@@ -223,6 +223,28 @@ void abpoa_amd_get_stats(uint64_t *dp_cells, uint64_t *kernel_ns, uint64_t *n_la
 void abpoa_amd_get_stats2(uint64_t *alg_bytes);
 void abpoa_amd_reset_stats(void);
 
+/* Consensus stage of the batched driver. With the default configuration
+ * (cons_algrm == ABPOA_HB, max_n_cons == 1) the device-resident driver
+ * computes each set's consensus on the GPU after the last round and downloads
+ * only the consensus (node ids, bases, coverage; phred is derived on the host
+ * from the coverage). Every other configuration, a set with no graph, and any
+ * set whose device job reports a non-OK status download the set's graph and
+ * run abpoa_generate_consensus on host threads instead. Setting the
+ * environment variable ABPOA_AMD_HOST_CONS (any value; read on every batch
+ * call) forces that download path for all sets — outputs are identical, it
+ * exists for A/B measurement.
+ *
+ * Counters are cumulative since the last reset:
+ *   device_sets    sets whose consensus came from the device kernel
+ *   host_sets      sets that took the graph-download path, for any reason
+ *   fallback_sets  the subset of host_sets caused by a non-OK device status
+ *   d2h_bytes      bytes the consensus stage copied device-to-host (either path)
+ *   kernel_ns      consensus kernel time, measured with HIP events
+ * Any pointer may be NULL. Builds without the GPU core report zeros. */
+void abpoa_amd_get_cons_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_t *fallback_sets,
+                              uint64_t *d2h_bytes, uint64_t *kernel_ns);
+void abpoa_amd_reset_cons_stats(void);
+
 #ifdef __cplusplus
 }
 #endif
