@@ -79,10 +79,33 @@ def reset_cons_stats():
     L.abpoa_amd_reset_cons_stats()
 
 
+def get_msa_stats():
+    """Row-column MSA counters of the batched driver since the last reset, for
+    calls with out_msa only: dict(device_sets, host_sets, fallback_sets,
+    d2h_bytes, kernel_ns). device_sets had their rows built by the GPU MSA
+    kernels; host_sets downloaded their graph for abpoa_generate_rc_msa
+    (fallback_sets of them after a non-OK device status)."""
+    L = lib()
+    L.abpoa_amd_get_msa_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)] * 5
+    L.abpoa_amd_get_msa_stats.restype = None
+    v = [ctypes.c_uint64() for _ in range(5)]
+    L.abpoa_amd_get_msa_stats(*[ctypes.byref(x) for x in v])
+    keys = ("device_sets", "host_sets", "fallback_sets", "d2h_bytes", "kernel_ns")
+    return dict(zip(keys, (x.value for x in v)))
+
+
+def reset_msa_stats():
+    L = lib()
+    L.abpoa_amd_reset_msa_stats.restype = None
+    L.abpoa_amd_reset_msa_stats()
+
+
 _ACGT = "ACGTN-"
+_ROW_TR = bytes(_ACGT.encode("ascii") + b"?" * (256 - len(_ACGT)))
 
 
-def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1):
+def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1,
+                      out_msa=False, out_cons=True):
     """Run the batched GPU driver over `sets` (list of list of bytes, codes
     0..3) and return, per set, the full callback payload as a dict:
       cons          list of consensus strings (one per cluster)
@@ -92,7 +115,14 @@ def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1):
       n_seq         reads in the set
     cons_algrm: None = library default (HB), "MF" = most-frequent (exercises
     the per-edge read-id bitsets on the device-resident path).
-    max_n_cons: 1 or 2 consensus sequences per set."""
+    max_n_cons: 1 or 2 consensus sequences per set.
+    out_msa: also build the row-column MSA; each result then additionally holds
+      msa_len       number of columns
+      msa           list of row strings over "ACGTN-": the read rows, then
+                    (with out_cons) the consensus rows
+    out_cons: with out_msa, whether the consensus rows are part of the MSA
+    (the consensus itself is always delivered). Results without out_msa keep
+    exactly the keys listed first."""
     L = lib()
     L.abpoa_init_para.restype = ctypes.c_void_p
     L.abpoa_post_set_para.argtypes = [ctypes.c_void_p]
@@ -104,7 +134,7 @@ def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1):
         ctypes.POINTER(ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))),
         CONS_CB, ctypes.c_void_p, ctypes.c_int]
     para = L.abpoa_init_para()
-    if cons_algrm is not None or max_n_cons != 1:
+    if cons_algrm is not None or max_n_cons != 1 or out_msa:
         from .pyabpoa import ParaT, ABPOA_HB, ABPOA_MF
         p = ctypes.cast(para, ctypes.POINTER(ParaT)).contents
         if cons_algrm is not None:
@@ -113,6 +143,10 @@ def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1):
             if max_n_cons < 1 or max_n_cons > 2:
                 raise ValueError("max_n_cons must be 1 or 2")
             p.max_n_cons = max_n_cons
+        if out_msa:
+            # before abpoa_post_set_para, which switches read-id tracking on
+            p.out_msa = 1
+            p.out_cons = 1 if out_cons else 0
     L.abpoa_post_set_para(para)
 
     n_sets = len(sets)
@@ -144,6 +178,13 @@ def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1):
             r["phred"].append(c.cons_phred_score[ci][:ln])
             r["clu_n_seq"].append(c.clu_n_seq[ci])
             r["clu_read_ids"].append(c.clu_read_ids[ci][:c.clu_n_seq[ci]])
+        if out_msa:
+            # rows are valid only during the callback: copy them out here
+            ln = c.msa_len
+            n_rows = c.n_seq + (c.n_cons if out_cons else 0) if ln > 0 else 0
+            r["msa_len"] = ln
+            r["msa"] = [ctypes.string_at(c.msa_base[i], ln).translate(_ROW_TR).decode("ascii")
+                        for i in range(n_rows)]
         out[idx] = r
 
     rc = L.abpoa_amd_msa_batch(para, n_sets, NSeqs, LensTop, SeqsTop, cb, None, n_threads)

@@ -114,6 +114,9 @@ static void cons_worker(void *arg, int tid, int nthr) {
         if (si >= w->n_sets) break;
         w->sets[si].ab->abs->n_seq = w->sets[si].n_seqs; /* consensus reads n_seq */
         abpoa_generate_consensus(w->sets[si].ab, w->abpt);
+        /* rows for the callback; the consensus above is kept (is_called_cons
+         * makes the call inside a no-op) and feeds the consensus rows */
+        if (w->abpt->out_msa) abpoa_generate_rc_msa(w->sets[si].ab, w->abpt);
     }
 }
 

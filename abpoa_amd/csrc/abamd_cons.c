@@ -613,6 +613,24 @@ void abamd_cons_from_path(abpoa_cons_t *abc, int n_seq, int cons_len, const int 
     free(phred_of);
 }
 
+/* Attach a downloaded row-major matrix as the msa_base rows
+ * abpoa_generate_rc_msa would have produced for the same graph: one
+ * allocation per row, n_seq + n_cons rows, so cons_clear frees it unchanged.
+ * The batch drivers always carry a consensus, so with out_cons off the matrix
+ * has only the read rows and the trailing rows are gap-filled. */
+void abamd_cons_attach_msa(abpoa_cons_t *abc, int n_rows, int msa_len, const uint8_t *rows,
+                           int gap) {
+    int i, total = abc->n_seq + abc->n_cons;
+    if (msa_len <= 0 || total <= 0) return;
+    abc->msa_len = msa_len;
+    abc->msa_base = (uint8_t**)abamd_malloc((size_t)total * sizeof(uint8_t*));
+    for (i = 0; i < total; ++i) {
+        abc->msa_base[i] = (uint8_t*)abamd_malloc((size_t)msa_len);
+        if (i < n_rows) memcpy(abc->msa_base[i], rows + (size_t)i * msa_len, (size_t)msa_len);
+        else memset(abc->msa_base[i], gap, (size_t)msa_len);
+    }
+}
+
 /* node msa rank = max over its aligned group (abpoa_output.c:136-144) */
 static int group_msa_rank(abpoa_graph_t *g, int id) {
     int k, rank = g->node_id_to_msa_rank[id];

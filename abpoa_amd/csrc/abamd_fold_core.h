@@ -31,6 +31,14 @@ enum {
 };
 #define ABAMD_CONS_CHUNK 64
 
+/* phased flat row-column MSA (abamd_msa_core.inc): per-job status */
+enum {
+    ABAMD_MSA_OK = 0,
+    ABAMD_MSA_BAD_GRAPH = 1      /* an index out of its pool, a walk past its
+                                    bound, a read id >= n_seq or a column
+                                    outside the matrix: only a corrupt graph */
+};
+
 /* Device translation units (gpu_fold.hip) include this header for the
  * flat_graph_t layout only: the function bodies there are __device__ builds
  * of abamd_fold_core.inc, and host declarations of the same names would
@@ -75,13 +83,35 @@ int abamd_flat_cons_phased(const flat_graph_t *fg, const int *i2n, const int *n2
                            int *cons_id, uint8_t *cons_base, int *cons_cov,
                            int *stage, int *cons_len_out, int lane, int n_lanes);
 
+/* row-column MSA in two stages over the flat graph (abamd_msa_core.inc);
+ * host build of the device kernels' bodies — call with lane 0 of 1.
+ * Stage 1: rank/col/in_deg/stack hold node_n ints each, stage 2 ints; yields
+ * msa_len and each node's column in col[]. Stage 2: msa is a row-major
+ * (n_seq + (cons_len >= 0)) x msa_len matrix pre-filled with the gap code.
+ * Both return ABAMD_MSA_*. */
+int abamd_flat_msa_rank_cols(const flat_graph_t *fg, int *rank, int *col,
+                             int *in_deg, int *stack, int *stage,
+                             int *msa_len_out, int lane, int n_lanes);
+int abamd_flat_msa_place(const flat_graph_t *fg, const int *col, int n_seq,
+                         int msa_len, uint8_t *msa, const int *cons_id,
+                         const uint8_t *cons_base, int cons_len,
+                         int *stage, int lane, int n_lanes);
+
 #ifdef ABPOA_AMD_H
 /* Build the single-cluster abpoa_cons_t the heaviest-bundle pass produces
  * from a consensus path (abamd_cons.c): phred from coverage on the host,
  * n_cons = 1, every read in cluster 0. `abc` must be cleared. */
 void abamd_cons_from_path(abpoa_cons_t *abc, int n_seq, int cons_len, const int *ids,
                           const uint8_t *bases, const int *cov);
-/* free an abpoa_cons_t's arrays and zero it (abamd_graph.c) */
+/* Attach a row-column MSA to a result built by abamd_cons_from_path
+ * (abamd_cons.c): `rows` is a row-major n_rows x msa_len matrix with
+ * n_rows = n_seq, or n_seq + n_cons with the consensus rows last. msa_base
+ * gets n_seq + n_cons separately allocated rows, the layout
+ * abpoa_generate_rc_msa produces and abamd_cons_clear frees; rows beyond
+ * n_rows hold the gap code. */
+void abamd_cons_attach_msa(abpoa_cons_t *abc, int n_rows, int msa_len, const uint8_t *rows,
+                           int gap);
+/* free an abpoa_cons_t's arrays, MSA rows included, and zero it (abamd_graph.c) */
 void abamd_cons_clear(abpoa_cons_t *abc);
 /* Rebuild a pointer graph from a (host copy of a) flat graph and topo-sort
  * it — the device-resident batch driver's hand-off to the host consensus

@@ -19,7 +19,9 @@
  *   - queries upload once (whole batch), not once per round;
  *   - after the last round the default configuration (heaviest bundle, one
  *     consensus) runs the consensus kernel (gpu_fold.hip) on the final graphs
- *     and downloads only each set's consensus; every other configuration,
+ *     and downloads only each set's consensus (with abpt->out_msa, two more
+ *     kernels build the row-column MSA there and only the matrix comes
+ *     down); every other configuration, ABPOA_AMD_HOST_MSA,
  *     ABPOA_AMD_HOST_CONS, and any set whose device job is not OK download
  *     the flat graph once and rebuild a pointer graph (abamd_graph_from_flat)
  *     for the existing host consensus.
@@ -64,6 +66,9 @@ namespace {
  * calls and threads until reset */
 std::atomic<uint64_t> g_cons_device_sets{0}, g_cons_host_sets{0}, g_cons_fallback_sets{0},
                       g_cons_d2h_bytes{0}, g_cons_kernel_ns{0};
+/* row-column MSA counters (abpoa_amd_get_msa_stats): only out_msa calls count */
+std::atomic<uint64_t> g_msa_device_sets{0}, g_msa_host_sets{0}, g_msa_fallback_sets{0},
+                      g_msa_d2h_bytes{0}, g_msa_kernel_ns{0};
 
 uint64_t g_held; /* bytes held by this driver's reusable device buffers */
 double g_alloc_s; long g_alloc_n; /* hipMalloc churn diagnostics */
@@ -729,6 +734,9 @@ struct HostCons {
                                                c.hi2n[s], c.hn2i[s], c.hrem[s]);
             ab->abs->n_seq = c.B.sets[s].n_seqs;
             abpoa_generate_consensus(ab, c.B.abpt);
+            /* rows for the callback; the consensus above is kept
+             * (is_called_cons makes the call inside a no-op) */
+            if (c.B.abpt->out_msa) abpoa_generate_rc_msa(ab, c.B.abpt);
             c.abs[s] = ab;
         }
     }
@@ -855,6 +863,143 @@ void device_consensus(Batch &B, Slot &S, const std::vector<int> &list,
     }
 }
 
+/* Device row-column MSA for `list` (sets whose device consensus succeeded;
+ * cons[s] holds it). Launch A (abamd_msa_rank_kernel) on slot S's stream —
+ * the stream the consensus kernel ran on — leaves every node's column in the
+ * slab and reports {status, msa_len}; the host then lays the exact-size
+ * matrices out in the slot's DP arena (dead after the last round and far
+ * larger than needed), fills them with the gap code, and launch B
+ * (abamd_msa_place_kernel) writes the rows, which are the only bulk download.
+ * Sets are processed in chunks bounded by the arena and by MSA_STAGE_MAX of
+ * pinned staging. Workspaces are slab regions that are dead once the
+ * consensus kernel has run and that are NOT consensus outputs: rank =
+ * pre_off, col = out_off (node_cap + 1 ints each), in-degree + stack =
+ * scratch (2 * node_cap ints); the consensus ids/bases the place kernel reads
+ * stay in row_remain / max_right. carve() sizes all of these from node_cap,
+ * so the mapping holds on an expanded slab too. The graph pools are only
+ * read: a set whose job comes back non-OK (returned in `fallback`) can still
+ * take the host path. */
+const size_t MSA_STAGE_MAX = (size_t)256 << 20;
+
+void device_msa(Batch &B, Slot &S, const std::vector<int> &list,
+                std::vector<abpoa_cons_t> &cons, std::vector<int> &fallback,
+                uint64_t &d2h_bytes, double &kernel_ms) {
+    const int n_jobs = (int)list.size();
+    if (n_jobs == 0) return;
+    Ctx &C = g_ctx;
+    abpoa_para_t *abpt = B.abpt;
+    const int cons_row = abpt->out_cons ? 1 : 0;
+    std::vector<abamd_msa_job_t> hj(n_jobs);
+    S.d_fjobs.ensure((size_t)n_jobs * sizeof(abamd_msa_job_t));
+    S.d_fouts.ensure((size_t)n_jobs * sizeof(abamd_msa_out_t));
+    for (int i = 0; i < n_jobs; ++i) {
+        SetState &st = B.sets[list[i]];
+        abamd_msa_job_t &j = hj[i];
+        memset(&j, 0, sizeof(j));
+        j.g = st.g;
+        j.rank = st.pre_off;
+        j.col = st.out_off;
+        j.in_deg = st.scratch;
+        j.stack = st.scratch + st.g.node_cap;
+        j.cons_id = st.row_remain;
+        j.cons_base = (const uint8_t*)st.max_right;
+        j.cons_len = cons_row ? cons[list[i]].cons_len[0] : -1;
+        j.n_seq = st.n_seqs;
+        j.out = (abamd_msa_out_t*)S.d_fouts.p + i;
+    }
+    auto account = [&]() {
+        float ms = 0.f, t1 = 0.f, t2 = 0.f;
+        RHIP_CHECK(hipEventElapsedTime(&ms, S.ev1, S.ev2));
+        RHIP_CHECK(hipEventElapsedTime(&t1, C.ev_base, S.ev1));
+        RHIP_CHECK(hipEventElapsedTime(&t2, C.ev_base, S.ev2));
+        C.spans.push_back({t1, t2});
+        kernel_ms += ms;
+    };
+    const size_t job_bytes = (size_t)n_jobs * sizeof(abamd_msa_job_t);
+    const size_t out_bytes = (size_t)n_jobs * sizeof(abamd_msa_out_t);
+    S.h_stage.ensure(job_bytes);
+    memcpy(S.h_stage.p, hj.data(), job_bytes);
+    RHIP_CHECK(hipMemcpyAsync(S.d_fjobs.p, S.h_stage.p, job_bytes, hipMemcpyHostToDevice, S.stream));
+    RHIP_CHECK(hipEventRecord(S.ev1, S.stream));
+    abamd_launch_msa_rank((const abamd_msa_job_t*)S.d_fjobs.p, n_jobs, S.stream);
+    RHIP_CHECK(hipGetLastError());
+    RHIP_CHECK(hipEventRecord(S.ev2, S.stream));
+    S.h_read.ensure(out_bytes);
+    RHIP_CHECK(hipMemcpyAsync(S.h_read.p, S.d_fouts.p, out_bytes, hipMemcpyDeviceToHost, S.stream));
+    RHIP_CHECK(hipStreamSynchronize(S.stream));
+    d2h_bytes += out_bytes;
+    account();
+
+    /* exact matrix sizes from the records */
+    std::vector<abamd_msa_out_t> outs(n_jobs);
+    memcpy(outs.data(), S.h_read.p, out_bytes);
+    std::vector<size_t> bytes(n_jobs, 0);
+    size_t max_one = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const SetState &st = B.sets[list[i]];
+        if (outs[i].status == ABAMD_MSA_OK && outs[i].msa_len >= 1 &&
+            outs[i].msa_len <= st.g.node_n - 2 && st.n_seqs > 0) {
+            bytes[i] = al16((size_t)(st.n_seqs + cons_row) * (size_t)outs[i].msa_len);
+            if (bytes[i] > max_one) max_one = bytes[i];
+        } else {
+            outs[i].status = ABAMD_MSA_BAD_GRAPH;
+        }
+    }
+    size_t limit = std::min(S.arena.cap, MSA_STAGE_MAX);
+    if (limit < max_one) {      /* no arena yet, or one set above the bound */
+        S.arena.ensure(max_one);
+        limit = max_one;
+    }
+
+    std::vector<abamd_msa_job_t> cj;
+    std::vector<int> cidx;
+    std::vector<size_t> coff;
+    int i0 = 0;
+    while (i0 < n_jobs) {
+        size_t acc = 0;
+        int i1 = i0;
+        cj.clear(); cidx.clear(); coff.clear();
+        for (; i1 < n_jobs; ++i1) {
+            if (outs[i1].status != ABAMD_MSA_OK) { fallback.push_back(list[i1]); continue; }
+            if (acc && acc + bytes[i1] > limit) break;
+            abamd_msa_job_t j = hj[i1];
+            j.msa = (uint8_t*)S.arena.p + acc;
+            j.msa_len = outs[i1].msa_len;
+            j.out = (abamd_msa_out_t*)S.d_fouts.p + cj.size();
+            cj.push_back(j);
+            cidx.push_back(i1);
+            coff.push_back(acc);
+            acc += bytes[i1];
+        }
+        i0 = i1;
+        if (cj.empty()) continue;
+        const int nc = (int)cj.size();
+        const size_t cjb = (size_t)nc * sizeof(abamd_msa_job_t);
+        const size_t cob = al16((size_t)nc * sizeof(abamd_msa_out_t));
+        memcpy(S.h_stage.p, cj.data(), cjb);
+        RHIP_CHECK(hipMemcpyAsync(S.d_fjobs.p, S.h_stage.p, cjb, hipMemcpyHostToDevice, S.stream));
+        RHIP_CHECK(hipMemsetAsync(S.arena.p, abpt->m, acc, S.stream));
+        RHIP_CHECK(hipEventRecord(S.ev1, S.stream));
+        abamd_launch_msa_place((const abamd_msa_job_t*)S.d_fjobs.p, nc, S.stream);
+        RHIP_CHECK(hipGetLastError());
+        RHIP_CHECK(hipEventRecord(S.ev2, S.stream));
+        S.h_read.ensure(cob + acc);
+        RHIP_CHECK(hipMemcpyAsync(S.h_read.p, S.d_fouts.p, (size_t)nc * sizeof(abamd_msa_out_t),
+                                  hipMemcpyDeviceToHost, S.stream));
+        RHIP_CHECK(hipMemcpyAsync(S.h_read.p + cob, S.arena.p, acc, hipMemcpyDeviceToHost, S.stream));
+        RHIP_CHECK(hipStreamSynchronize(S.stream));
+        d2h_bytes += (size_t)nc * sizeof(abamd_msa_out_t) + acc;
+        account();
+        const abamd_msa_out_t *po = (const abamd_msa_out_t*)S.h_read.p;
+        for (int k = 0; k < nc; ++k) {
+            const int s = list[cidx[k]];
+            if (po[k].status != ABAMD_MSA_OK) { fallback.push_back(s); continue; }
+            abamd_cons_attach_msa(&cons[s], B.sets[s].n_seqs + cons_row, cj[k].msa_len,
+                                  S.h_read.p + cob + coff[k], abpt->m);
+        }
+    }
+}
+
 } // namespace
 
 /* ------------------------------------------------------------------ */
@@ -906,6 +1051,19 @@ extern "C" void abpoa_amd_get_cons_stats(uint64_t *device_sets, uint64_t *host_s
 extern "C" void abpoa_amd_reset_cons_stats(void) {
     g_cons_device_sets = 0; g_cons_host_sets = 0; g_cons_fallback_sets = 0;
     g_cons_d2h_bytes = 0; g_cons_kernel_ns = 0;
+}
+
+extern "C" void abpoa_amd_get_msa_stats(uint64_t *device_sets, uint64_t *host_sets,
+        uint64_t *fallback_sets, uint64_t *d2h_bytes, uint64_t *kernel_ns) {
+    if (device_sets) *device_sets = g_msa_device_sets.load();
+    if (host_sets) *host_sets = g_msa_host_sets.load();
+    if (fallback_sets) *fallback_sets = g_msa_fallback_sets.load();
+    if (d2h_bytes) *d2h_bytes = g_msa_d2h_bytes.load();
+    if (kernel_ns) *kernel_ns = g_msa_kernel_ns.load();
+}
+extern "C" void abpoa_amd_reset_msa_stats(void) {
+    g_msa_device_sets = 0; g_msa_host_sets = 0; g_msa_fallback_sets = 0;
+    g_msa_d2h_bytes = 0; g_msa_kernel_ns = 0;
 }
 
 extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, const int *n_seqs,
@@ -1225,8 +1383,13 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     /* ---- consensus: on the device where the configuration allows, else
      * (and per set on a non-OK device status) graph download + host pass ---- */
     double t_cons0 = abamd_realtime();
+    /* with out_msa a set is device for both stages or host for both:
+     * ABPOA_AMD_HOST_MSA (or rows requested without read-id tracking, which
+     * only the host path reproduces) sends every set to the download path */
+    const bool want_msa = abpt->out_msa;
     const bool dev_cons = abpt->cons_algrm == ABPOA_HB && abpt->max_n_cons == 1 &&
-                          !getenv("ABPOA_AMD_HOST_CONS");
+                          !getenv("ABPOA_AMD_HOST_CONS") &&
+                          !(want_msa && (getenv("ABPOA_AMD_HOST_MSA") || !abpt->use_read_ids));
     std::vector<int> dev_list, host_list, fallback;
     for (int s = 0; s < n_sets; ++s) {
         if (dev_cons && B.sets[s].g.node_n > 2) dev_list.push_back(s);
@@ -1238,6 +1401,21 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     uint64_t cons_d2h = 0;
     double cons_kernel_ms = 0;
     device_consensus(B, S0, dev_list, dcons, fallback, cons_d2h, cons_kernel_ms);
+    uint64_t msa_d2h = 0;
+    double msa_kernel_ms = 0;
+    if (want_msa && !dev_list.empty()) {
+        /* same stream, after the consensus kernel; a set that fails here
+         * gives up its device consensus too and joins the fallback list */
+        std::vector<char> cons_failed(n_sets, 0);
+        for (int s : fallback) cons_failed[s] = 1;
+        std::vector<int> msa_list, msa_fallback;
+        for (int s : dev_list) if (!cons_failed[s]) msa_list.push_back(s);
+        device_msa(B, S0, msa_list, dcons, msa_fallback, msa_d2h, msa_kernel_ms);
+        for (int s : msa_fallback) {
+            abamd_cons_clear(&dcons[s]);
+            fallback.push_back(s);
+        }
+    }
     for (int s : dev_list) from_device[s] = 1;
     for (int s : fallback) from_device[s] = 0;
     HostCons hc(B);
@@ -1253,6 +1431,16 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     g_cons_fallback_sets += n_fallback;
     g_cons_d2h_bytes += cons_d2h;
     g_cons_kernel_ns += (uint64_t)(cons_kernel_ms * 1e6);
+    if (want_msa) {
+        /* the host path's rows cost the graph download (shared with the
+         * consensus, reported in both sets of counters) */
+        msa_d2h += hc.d2h_bytes;
+        g_msa_device_sets += n_dev;
+        g_msa_host_sets += n_host;
+        g_msa_fallback_sets += n_fallback;
+        g_msa_d2h_bytes += msa_d2h;
+        g_msa_kernel_ns += (uint64_t)(msa_kernel_ms * 1e6);
+    }
     if (cb)
         for (int s = 0; s < n_sets; ++s)
             cb(s, from_device[s] ? &dcons[s] : hc.abs[s]->abc, user);
@@ -1278,6 +1466,12 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
                 cons_kernel_ms, (unsigned long long)cons_d2h,
                 (unsigned long long)n_dev, (unsigned long long)n_host,
                 (unsigned long long)n_fallback);
+        if (want_msa)
+            fprintf(stderr, "[abamd timing resident] msa-kernel %.2fms msa-d2h %llu B "
+                            "msa-sets device %llu host %llu fallback %llu\n",
+                    msa_kernel_ms, (unsigned long long)msa_d2h,
+                    (unsigned long long)n_dev, (unsigned long long)n_host,
+                    (unsigned long long)n_fallback);
         fprintf(stderr, "[abamd timing resident] hipMalloc %ld calls %.2fs\n",
                 g_alloc_n, g_alloc_s);
     }

@@ -82,6 +82,38 @@ typedef struct {
 
 void abamd_launch_cons(const abamd_cons_job_t *dev_jobs, int n_jobs, void *stream);
 
+/* ---- device row-column MSA (gpu_fold.hip :: abamd_msa_rank_kernel,
+ * abamd_msa_place_kernel) ----
+ * One job = one read set's FINAL graph, after abamd_cons_kernel on the same
+ * stream. Launch A (rank) fills col[] and writes {status, msa_len}; the host
+ * reads the records, lays the exact-size matrices out in one device buffer
+ * pre-filled with the gap code, sets msa/msa_len in the jobs and runs launch
+ * B (place), which writes the read rows and, when cons_len >= 0, one
+ * consensus row from the ids and bases the consensus kernel left in the
+ * slab, then overwrites `out->status`. The graph pools are only read; the
+ * workspaces are slab regions that are dead once the consensus kernel has
+ * run, and none of them is a consensus output. */
+typedef struct {
+    int32_t status;              /* ABAMD_MSA_* (abamd_fold_core.h) */
+    int32_t msa_len;
+} abamd_msa_out_t;
+
+typedef struct {
+    flat_graph_t g;              /* device ptrs; counters = host mirror */
+    int *rank, *col;             /* node space, >= node_n ints each */
+    int *in_deg, *stack;         /* node space, >= node_n ints each */
+    const int *cons_id;          /* consensus kernel outputs (place only) */
+    const uint8_t *cons_base;
+    int cons_len;                /* < 0: no consensus row */
+    int n_seq;
+    uint8_t *msa;                /* (n_seq + (cons_len >= 0)) x msa_len, gap-filled */
+    int msa_len;
+    abamd_msa_out_t *out;
+} abamd_msa_job_t;
+
+void abamd_launch_msa_rank(const abamd_msa_job_t *dev_jobs, int n_jobs, void *stream);
+void abamd_launch_msa_place(const abamd_msa_job_t *dev_jobs, int n_jobs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

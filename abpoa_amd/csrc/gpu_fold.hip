@@ -47,6 +47,8 @@ typedef uint64_t abpoa_cigar_t;
 #define ABAMD_FC_BARRIER() __syncthreads()
 #define ABAMD_CONS_PHASED_ONLY
 #include "abamd_cons_core.inc"
+/* row-column MSA body: bounded and range-checked throughout, never aborts */
+#include "abamd_msa_core.inc"
 
 /* ------------------------------------------------------------------ */
 /* Round-1 validation kernel (kept: the GPU twin test drives it).      */
@@ -518,6 +520,63 @@ void abamd_cons_kernel(const abamd_cons_job_t *jobs, int n_jobs) {
 
 extern "C" void abamd_launch_cons(const abamd_cons_job_t *dev_jobs, int n_jobs, void *stream) {
     hipLaunchKernelGGL(abamd_cons_kernel, dim3(n_jobs), dim3(FOLD_WAVE), 0,
+                       (hipStream_t)stream, dev_jobs, n_jobs);
+}
+
+/* ------------------------------------------------------------------ */
+/* Device row-column MSA kernels.                                      */
+/* ------------------------------------------------------------------ */
+
+/* One 64-lane workgroup per set, like the fold and consensus kernels: the
+ * rank walk is serial pointer chasing on lane 0 (its LIFO pop order IS the
+ * column order, so the fold's topological order cannot stand in for it), and
+ * cross-set parallelism fills the chip. Two launches so that the matrix
+ * buffer is sized from the msa_len the first one reports.
+ *
+ * Launch A: in-degrees (lane-parallel), bounded rank walk (lane 0), columns
+ * (lane-parallel); record {status, msa_len}. LDS: 2 ints. */
+extern "C" __global__ __launch_bounds__(FOLD_WAVE)
+void abamd_msa_rank_kernel(const abamd_msa_job_t *jobs, int n_jobs) {
+    __shared__ int stage[2];
+    const int j = blockIdx.x;
+    if (j >= n_jobs) return;
+    const abamd_msa_job_t *job = &jobs[j];
+    const flat_graph_t gl = job->g; /* by value: pool pointers in registers */
+    int msa_len = 0;
+    const int status = abamd_flat_msa_rank_cols(&gl, job->rank, job->col, job->in_deg,
+                                                job->stack, stage, &msa_len,
+                                                (int)threadIdx.x, FOLD_WAVE);
+    if (threadIdx.x == 0) {
+        job->out->status = status;
+        job->out->msa_len = msa_len;
+    }
+}
+
+/* Launch B: every node >= 2 stores its base at (read, column) for each read
+ * bit on its out-edges, then the consensus row; plain stores, no atomics
+ * (abamd_msa_core.inc explains why no two stores meet). Every store is
+ * bounds-checked against n_seq and msa_len; a violation sets the job's
+ * status instead. LDS: 2 ints. */
+extern "C" __global__ __launch_bounds__(FOLD_WAVE)
+void abamd_msa_place_kernel(const abamd_msa_job_t *jobs, int n_jobs) {
+    __shared__ int stage[2];
+    const int j = blockIdx.x;
+    if (j >= n_jobs) return;
+    const abamd_msa_job_t *job = &jobs[j];
+    const flat_graph_t gl = job->g;
+    const int status = abamd_flat_msa_place(&gl, job->col, job->n_seq, job->msa_len, job->msa,
+                                            job->cons_id, job->cons_base, job->cons_len,
+                                            stage, (int)threadIdx.x, FOLD_WAVE);
+    if (threadIdx.x == 0) job->out->status = status;
+}
+
+extern "C" void abamd_launch_msa_rank(const abamd_msa_job_t *dev_jobs, int n_jobs, void *stream) {
+    hipLaunchKernelGGL(abamd_msa_rank_kernel, dim3(n_jobs), dim3(FOLD_WAVE), 0,
+                       (hipStream_t)stream, dev_jobs, n_jobs);
+}
+
+extern "C" void abamd_launch_msa_place(const abamd_msa_job_t *dev_jobs, int n_jobs, void *stream) {
+    hipLaunchKernelGGL(abamd_msa_place_kernel, dim3(n_jobs), dim3(FOLD_WAVE), 0,
                        (hipStream_t)stream, dev_jobs, n_jobs);
 }
 

@@ -48,6 +48,16 @@ void abpoa_amd_get_cons_stats(uint64_t *device_sets, uint64_t *host_sets, uint64
     if (kernel_ns) *kernel_ns = 0;
 }
 void abpoa_amd_reset_cons_stats(void) {}
+/* nor a device MSA: the host-fold driver builds the rows on host threads */
+void abpoa_amd_get_msa_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_t *fallback_sets,
+                             uint64_t *d2h_bytes, uint64_t *kernel_ns) {
+    if (device_sets) *device_sets = 0;
+    if (host_sets) *host_sets = 0;
+    if (fallback_sets) *fallback_sets = 0;
+    if (d2h_bytes) *d2h_bytes = 0;
+    if (kernel_ns) *kernel_ns = 0;
+}
+void abpoa_amd_reset_msa_stats(void) {}
 void abamd_timing_report(const char *tag) { (void)tag; }
 
 static abamd_batch_job_t *stub_slot_batch[8];

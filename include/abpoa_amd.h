@@ -207,7 +207,16 @@ void abpoa_amd_set_test_aligner(abpoa_amd_aligner_fn fn);
  * GPU sees thousands of in-flight alignments. Processes sets[0..n_sets) where
  * each set is n_seqs sequences of seq_lens[s][i] bases (0..m-1 codes); writes
  * per-set consensus through the callback. Used by bench.py and the multi-GPU
- * sharding layer. */
+ * sharding layer.
+ *
+ * With abpt->out_msa set (before abpoa_post_set_para, so that read ids are
+ * tracked) the callback's abpoa_cons_t also carries the row-column MSA exactly
+ * as abpoa_generate_rc_msa produces it for the same graph: msa_len columns and
+ * msa_base rows of msa_len bytes each — n_seq read rows, followed by n_cons
+ * consensus rows when abpt->out_cons is set — with gaps coded abpt->m. The
+ * rows, like the rest of the result, are valid only during the callback. A
+ * set with no graph has msa_len == 0. Without out_msa the result has
+ * msa_len == 0 and msa_base == NULL, and no MSA work is done. */
 typedef void (*abpoa_amd_cons_cb)(int set_idx, const abpoa_cons_t *cons, void *user);
 int abpoa_amd_msa_batch(abpoa_para_t *abpt, int n_sets, const int *n_seqs,
         const int *const *seq_lens, const uint8_t *const *const *seqs,
@@ -244,6 +253,32 @@ void abpoa_amd_reset_stats(void);
 void abpoa_amd_get_cons_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_t *fallback_sets,
                               uint64_t *d2h_bytes, uint64_t *kernel_ns);
 void abpoa_amd_reset_cons_stats(void);
+
+/* Row-column MSA stage of the batched driver; only sets of calls with
+ * abpt->out_msa set are counted. A set takes the device path when it takes
+ * the device consensus path (above), has a graph, and the environment
+ * variable ABPOA_AMD_HOST_MSA is unset (any value; read on every batch call;
+ * it sends every set to the graph-download path for consensus AND rows —
+ * outputs are identical, it exists for A/B measurement). On the device path
+ * two kernels build the matrix from the resident graph and only the matrix
+ * is downloaded. A set is device for both stages or host for both: if either
+ * device job reports a non-OK status that set alone falls back, and it is
+ * counted as a fallback here and in the consensus counters.
+ *
+ * Counters are cumulative since the last reset:
+ *   device_sets    sets whose rows came from the device kernels
+ *   host_sets      sets whose rows came from abpoa_generate_rc_msa on a
+ *                  downloaded graph, for any reason
+ *   fallback_sets  the subset of host_sets caused by a non-OK device status
+ *   d2h_bytes      bytes the rows cost device-to-host: per-set records plus
+ *                  the matrix on the device path; the graph download on the
+ *                  host path (that one download also serves the consensus and
+ *                  is reported in the consensus counters too, as before)
+ *   kernel_ns      MSA kernel time (both launches), measured with HIP events
+ * Any pointer may be NULL. Builds without the GPU core report zeros. */
+void abpoa_amd_get_msa_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_t *fallback_sets,
+                             uint64_t *d2h_bytes, uint64_t *kernel_ns);
+void abpoa_amd_reset_msa_stats(void);
 
 #ifdef __cplusplus
 }
