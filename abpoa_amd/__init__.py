@@ -100,6 +100,27 @@ def reset_msa_stats():
     L.abpoa_amd_reset_msa_stats()
 
 
+def get_fold_stats():
+    """Graph-fold counters of the batched driver since the last reset:
+    dict(parallel_folds, fallback_folds, serial_folds). parallel_folds ran the
+    lane-parallel mutation walk; fallback_folds tripped one of its checks and
+    were redone by the serial walk; serial_folds ran the serial walk because
+    ABPOA_AMD_SERIAL_FOLD was set."""
+    L = lib()
+    L.abpoa_amd_get_fold_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)] * 3
+    L.abpoa_amd_get_fold_stats.restype = None
+    v = [ctypes.c_uint64() for _ in range(3)]
+    L.abpoa_amd_get_fold_stats(*[ctypes.byref(x) for x in v])
+    keys = ("parallel_folds", "fallback_folds", "serial_folds")
+    return dict(zip(keys, (x.value for x in v)))
+
+
+def reset_fold_stats():
+    L = lib()
+    L.abpoa_amd_reset_fold_stats.restype = None
+    L.abpoa_amd_reset_fold_stats()
+
+
 _ACGT = "ACGTN-"
 _ROW_TR = bytes(_ACGT.encode("ascii") + b"?" * (256 - len(_ACGT)))
 

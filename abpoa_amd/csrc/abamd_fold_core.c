@@ -58,5 +58,6 @@ void abamd_flat_free(flat_graph_t *fg) {
 
 
 #include "abamd_fold_core.inc"
+#include "abamd_fold_par.inc"
 #include "abamd_cons_core.inc"
 #include "abamd_msa_core.inc"

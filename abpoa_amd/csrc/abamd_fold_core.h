@@ -39,6 +39,35 @@ enum {
                                     outside the matrix: only a corrupt graph */
 };
 
+/* lane-parallel mutation walk (abamd_fold_par.inc): scratch and per-call
+ * state. The six arrays hold `cap` ints each, `part` holds part_cap >=
+ * ABAMD_PAR_PARTS * n_lanes ints; none of them overlaps another or the graph. */
+#define ABAMD_PAR_PHASES 6
+#define ABAMD_PAR_PARTS 6
+/* part[k * n_lanes + lane]: violation flag, query bases consumed, new nodes,
+ * aligned-pool entries, last existing path node (-1: none), new edges */
+enum { FLAT_PAR_BAD = 0, FLAT_PAR_C, FLAT_PAR_NN, FLAT_PAR_NA, FLAT_PAR_LAST, FLAT_PAR_NE };
+typedef struct flat_par_ws_t {
+    int *owner;                  /* node id -> claiming op */
+    int *path, *nsp;             /* query pos -> path node, inherited n_span_read */
+    int *opres;                  /* op -> existing path node, or -1: creates one */
+    int *e_in, *e_out;           /* path edge -> existing edge id, or -1 */
+    int cap;
+    int *part; int part_cap;     /* per-lane partial sums and flags */
+} flat_par_ws_t;
+typedef struct flat_par_t {
+    flat_graph_t *fg;
+    int beg, end;
+    const uint8_t *seq; const int *weight; int seq_l;
+    int *qpos;
+    int n_cigar; const uint64_t *cig;
+    int read_id, add_read_id, inc_both_ends;
+    int node_n0, ein0, eout0, aln0;   /* counters before the walk */
+    int nn_tot, na_tot, ne_tot;       /* new nodes, aligned entries, edges */
+    flat_par_ws_t ws;
+    int mode, ok;
+} flat_par_t;
+
 /* Device translation units (gpu_fold.hip) include this header for the
  * flat_graph_t layout only: the function bodies there are __device__ builds
  * of abamd_fold_core.inc, and host declarations of the same names would
@@ -66,6 +95,22 @@ void abamd_flat_apply_alignment(flat_graph_t *fg, int beg_node_id, int end_node_
                                 const uint8_t *seq, const int *weight, int seq_l,
                                 int *qpos_to_node_id, int n_cigar, const abpoa_cigar_t *cig,
                                 int read_id, int add_read_id, int inc_both_ends);
+
+/* the same walk in lane-parallel phases (abamd_fold_par.inc). Returns 1 when
+ * applied, 0 when a guard tripped: the graph is untouched and the caller runs
+ * abamd_flat_apply_alignment. Host use: lane 0 of 1, or init + a loop over
+ * the lanes inside each of the ABAMD_PAR_PHASES phases to emulate a wave. */
+int abamd_flat_apply_par(flat_graph_t *fg, int beg_node_id, int end_node_id,
+                         const uint8_t *seq, const int *weight, int seq_l,
+                         int *qpos_to_node_id, int n_cigar, const abpoa_cigar_t *cig,
+                         int read_id, int add_read_id, int inc_both_ends,
+                         const flat_par_ws_t *ws, int lane, int n_lanes);
+void abamd_flat_par_init(flat_par_t *cx, flat_graph_t *fg, int beg_node_id, int end_node_id,
+                         const uint8_t *seq, const int *weight, int seq_l,
+                         int *qpos_to_node_id, int n_cigar, const abpoa_cigar_t *cig,
+                         int read_id, int add_read_id, int inc_both_ends,
+                         const flat_par_ws_t *ws, int n_lanes);
+void abamd_flat_par_phase(flat_par_t *cx, int phase, int lane, int n_lanes);
 
 /* single-cluster heaviest-bundle consensus over the flat layout
  * (abamd_cons_core.inc); returns cons_len */

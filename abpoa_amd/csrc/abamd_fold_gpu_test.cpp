@@ -9,7 +9,11 @@
  * already proven equal to the pointer graph. Passing here means the
  * round-2 device fold produces bit-identical graphs.
  *
- * Usage (GPU box): abpoa_amd_foldgpu reads.fa
+ * Usage (GPU box): abpoa_amd_foldgpu reads.fa [-p]
+ * -p runs abamd_fold_par_kernel instead: the lane-parallel mutation walk
+ * (abamd_fold_par.inc) across one 64-lane wave, then the same derived passes.
+ * The comparison is the same, plus chain tails and the qpos map, and no fold
+ * may fall back to the serial walk.
  */
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -42,7 +46,16 @@ typedef struct {
     int *msa_rank;
 } fold_job_t;
 
+/* must match gpu_fold.hip's fold_par_job_t */
+typedef struct {
+    fold_job_t j;
+    int *owner, *path, *nsp, *opres, *e_in, *e_out;
+    int ws_cap;
+    int *fallbacks;
+} fold_par_job_t;
+
 extern "C" __global__ void abamd_fold_kernel(fold_job_t *jobs, int n_jobs);
+extern "C" __global__ void abamd_fold_par_kernel(fold_par_job_t *jobs, int n_jobs);
 
 static void die(const char *what, int read_i) {
     fprintf(stderr, "DEVICE FOLD MISMATCH after read %d: %s\n", read_i, what);
@@ -50,7 +63,8 @@ static void die(const char *what, int read_i) {
 }
 
 int main(int argc, char **argv) {
-    if (argc < 2) { fprintf(stderr, "usage: %s reads.fa\n", argv[0]); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: %s reads.fa [-p]\n", argv[0]); return 2; }
+    const int par = argc > 2 && strcmp(argv[2], "-p") == 0;
     abpoa_para_t *abpt = abpoa_init_para();
     abpt->out_msa = 1; /* enable read-id tracking so bitsets are exercised */
     abpoa_post_set_para(abpt);
@@ -121,6 +135,16 @@ int main(int argc, char **argv) {
     DALLOC(d_msa_rank, node_cap, int);
     fold_job_t *d_job;
     DALLOC(d_job, 1, fold_job_t);
+    /* parallel-walk scratch: n_cigar <= qlen + rows, and seq_l + 1 edges */
+    fold_par_job_t pjob, *d_pjob;
+    memset(&pjob, 0, sizeof(pjob));
+    pjob.ws_cap = 2 * total_len + 66;
+    DALLOC(d_pjob, 1, fold_par_job_t);
+    DALLOC(pjob.owner, pjob.ws_cap, int); DALLOC(pjob.path, pjob.ws_cap, int);
+    DALLOC(pjob.nsp, pjob.ws_cap, int); DALLOC(pjob.opres, pjob.ws_cap, int);
+    DALLOC(pjob.e_in, pjob.ws_cap, int); DALLOC(pjob.e_out, pjob.ws_cap, int);
+    DALLOC(pjob.fallbacks, 1, int);
+    HIP_CHECK(hipMemset(pjob.fallbacks, 0, sizeof(int)));
 
     int *w = (int*)abamd_malloc((size_t)max_len * sizeof(int));
     for (i = 0; i < max_len; ++i) w[i] = 1;
@@ -161,11 +185,21 @@ int main(int argc, char **argv) {
         job.index_to_node_id = d_i2n; job.node_id_to_index = d_n2i;
         job.max_remain = d_rem; job.scratch = d_scr;
         job.msa_rank = d_msa_rank;
-        HIP_CHECK(hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(abamd_fold_kernel, dim3(1), dim3(64), 0, 0, d_job, 1);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(&job, d_job, sizeof(job), hipMemcpyDeviceToHost));
+        if (par) {
+            pjob.j = job;
+            HIP_CHECK(hipMemcpy(d_pjob, &pjob, sizeof(pjob), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(abamd_fold_par_kernel, dim3(1), dim3(64), 0, 0, d_pjob, 1);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(&pjob, d_pjob, sizeof(pjob), hipMemcpyDeviceToHost));
+            job = pjob.j;
+        } else {
+            HIP_CHECK(hipMemcpy(d_job, &job, sizeof(job), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(abamd_fold_kernel, dim3(1), dim3(64), 0, 0, d_job, 1);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(&job, d_job, sizeof(job), hipMemcpyDeviceToHost));
+        }
         dgh = job.g; /* counts mutated on device */
 
         /* feed the live graph for the next read's DP */
@@ -186,6 +220,11 @@ int main(int argc, char **argv) {
         CMP_ARR(dgh.in_head, hg.in_head, n, int, "in_head");
         CMP_ARR(dgh.out_head, hg.out_head, n, int, "out_head");
         CMP_ARR(dgh.aln_head, hg.aln_head, n, int, "aln_head");
+        if (par) {
+            CMP_ARR(dgh.in_tail, hg.in_tail, n, int, "in_tail");
+            CMP_ARR(dgh.out_tail, hg.out_tail, n, int, "out_tail");
+            CMP_ARR(d_qmap, h_qmap, qlen, int, "qpos_to_node_id");
+        }
         CMP_ARR(d_i2n, h_i2n, hg.node_n ? 1 + h_n2i[1] : 0, int, "topo index"); /* prefix up to sink */
         #define CMP_POOL(dptr, hptr, count, what) do { \
             HIP_CHECK(hipMemcpy(buf2, dptr, (size_t)(count) * sizeof(int), hipMemcpyDeviceToHost)); \
@@ -216,6 +255,14 @@ int main(int argc, char **argv) {
                 if (buf[id] != h_rem[id]) die("max_remain", i);
             }
         }
+    }
+    if (par) {
+        int fallbacks = 0;
+        HIP_CHECK(hipMemcpy(&fallbacks, pjob.fallbacks, sizeof(int), hipMemcpyDeviceToHost));
+        if (fallbacks) { fprintf(stderr, "DEVICE FOLD: %d folds fell back to the serial walk\n", fallbacks); return 1; }
+        printf("device fold OK (%d reads, %d nodes, %d out-edges; parallel walk, fallbacks 0)\n",
+               n_seq, hg.node_n, hg.edge_n_out);
+        return 0;
     }
     printf("device fold OK (%d reads, %d nodes, %d out-edges)\n", n_seq, hg.node_n, hg.edge_n_out);
     return 0;

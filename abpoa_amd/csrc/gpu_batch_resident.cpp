@@ -70,6 +70,16 @@ std::atomic<uint64_t> g_cons_device_sets{0}, g_cons_host_sets{0}, g_cons_fallbac
 std::atomic<uint64_t> g_msa_device_sets{0}, g_msa_host_sets{0}, g_msa_fallback_sets{0},
                       g_msa_d2h_bytes{0}, g_msa_kernel_ns{0};
 
+/* graph-fold counters (abpoa_amd_get_fold_stats): which mutation walk each
+ * settled fold job ran */
+std::atomic<uint64_t> g_fold_parallel{0}, g_fold_fallback{0}, g_fold_serial{0};
+
+void count_fold_walk(int walk) {
+    if (walk == ABAMD_FOLD_WALK_PARALLEL) g_fold_parallel += 1;
+    else if (walk == ABAMD_FOLD_WALK_FALLBACK) g_fold_fallback += 1;
+    else g_fold_serial += 1;
+}
+
 uint64_t g_held; /* bytes held by this driver's reusable device buffers */
 double g_alloc_s; long g_alloc_n; /* hipMalloc churn diagnostics */
 
@@ -151,7 +161,19 @@ struct SetState {
 inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 /* assign S's device pointers sequentially from `base`; returns bytes used.
- * Call with base = nullptr to size. Caps must already be set in S.g. */
+ * Call with base = nullptr to size. Caps must already be set in S.g.
+ *
+ * The fold kernel's lane-parallel mutation walk (abamd_fold_par.inc) takes
+ * its scratch from regions that are dead while it runs, so the slab does not
+ * grow for it: scratch[0, nc) = owner (indexed by node id < node_n),
+ * scratch[nc, 2nc) = path, row_remain = inherited n_span (both indexed by
+ * query position < seq_l), row_node_id = per-op result (n_cigar entries),
+ * pre_off / out_off = per-edge search results (seq_l + 1 entries). Each
+ * region holds >= nc ints and the walk is given cap = nc; the fold's capacity
+ * pre-check guarantees nc >= node_n + seq_l + 2, and a CIGAR has at most
+ * seq_l + n_rows <= seq_l + node_n ops (a longer one takes the serial walk).
+ * The CSR regions among them are rewritten by the same kernel's last pass;
+ * its early returns (DP skipped, no-op, pool overflow) come before the walk. */
 size_t carve(SetState &S, uint8_t *base) {
     size_t off = 0;
     const size_t nc = (size_t)S.g.node_cap, ec = (size_t)S.g.edge_cap, ac = (size_t)S.g.aln_cap;
@@ -273,6 +295,7 @@ struct Batch {
     std::vector<SetState> sets;
     int n_sets = 0, n_groups = 3;
     int use_remain = 0, planes = 5;
+    int serial_fold = 0;         /* ABPOA_AMD_SERIAL_FOLD: lane-0 mutation walk */
     double budget_bytes = 0;
     uint64_t retry_jobs = 0, pool_expands = 0;
     double t_host_build = 0, t_finish = 0;
@@ -369,6 +392,7 @@ void build_jobs(Batch &B, Slot &S, const std::vector<int> &set_list, int r,
         fj.out_idx = st.out_idx;
         fj.use_remain = B.use_remain;
         fj.m = abpt->m;
+        fj.serial_fold = B.serial_fold;
         /* cigar/dp_res/out wired in launch_slot once buffers are sized */
     }
     /* a mixed batch runs at the widest type; recompute inf_min at 32 bit */
@@ -519,6 +543,7 @@ void settle_fold(Batch &B, Slot &S, int i) {
             st.n_rows = fo->n_rows;
             st.n_pre = fo->n_pre;
             st.n_out = fo->n_out;
+            count_fold_walk(fo->walk);
             return;
         }
         if (fo->status == ABAMD_FOLD_NOOP) return; /* graph + CSR unchanged */
@@ -1066,6 +1091,16 @@ extern "C" void abpoa_amd_reset_msa_stats(void) {
     g_msa_d2h_bytes = 0; g_msa_kernel_ns = 0;
 }
 
+extern "C" void abpoa_amd_get_fold_stats(uint64_t *parallel_folds, uint64_t *fallback_folds,
+        uint64_t *serial_folds) {
+    if (parallel_folds) *parallel_folds = g_fold_parallel.load();
+    if (fallback_folds) *fallback_folds = g_fold_fallback.load();
+    if (serial_folds) *serial_folds = g_fold_serial.load();
+}
+extern "C" void abpoa_amd_reset_fold_stats(void) {
+    g_fold_parallel = 0; g_fold_fallback = 0; g_fold_serial = 0;
+}
+
 extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, const int *n_seqs,
         const int *const *seq_lens, const uint8_t *const *const *seqs,
         abpoa_amd_cons_cb cb, void *user, int n_host_threads) {
@@ -1084,6 +1119,7 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     B.abpt = abpt;
     B.n_sets = n_sets;
     B.use_remain = (abpt->wb >= 0 || abpt->zdrop > 0);
+    B.serial_fold = getenv("ABPOA_AMD_SERIAL_FOLD") ? 1 : 0;
     B.planes = abpt->gap_mode == ABPOA_CONVEX_GAP ? 3 /* F recomputed at backtrack */
              : abpt->gap_mode == ABPOA_AFFINE_GAP ? 3 : 1;
     B.sets.resize(n_sets);
@@ -1235,6 +1271,7 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
             fj.row_remain = st.row_remain; fj.pre_idx = st.pre_idx; fj.out_idx = st.out_idx;
             fj.use_remain = B.use_remain;
             fj.m = abpt->m;
+        fj.serial_fold = B.serial_fold;
             fj.out = (abamd_fold_out_t*)nullptr; /* wired below */
         }
         S.d_fjobs.ensure((size_t)n_jobs * sizeof(abamd_fold_round_job_t));
@@ -1280,6 +1317,7 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
             st.n_rows = fo->n_rows;
             st.n_pre = fo->n_pre;
             st.n_out = fo->n_out;
+            count_fold_walk(fo->walk);
         }
         S.active = false;
     }

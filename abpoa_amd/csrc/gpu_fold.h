@@ -35,7 +35,16 @@ typedef struct {
     int32_t status;
     int32_t node_n, edge_n_in, edge_n_out, aln_n;
     int32_t n_rows, n_pre, n_out; /* DP-row CSR sizes for the next round */
+    int32_t walk;                /* ABAMD_FOLD_WALK_*; set with status OK only */
 } abamd_fold_out_t;
+
+/* which mutation walk a fold job ran */
+enum {
+    ABAMD_FOLD_WALK_SERIAL = 0,  /* lane 0, on request (job.serial_fold) */
+    ABAMD_FOLD_WALK_PARALLEL = 1,/* abamd_fold_par.inc across the wave */
+    ABAMD_FOLD_WALK_FALLBACK = 2 /* parallel walk tripped a check: graph was
+                                    untouched, lane 0 redid it serially */
+};
 
 /* one fold job; all pointers are device pointers into the set's slab */
 typedef struct {
@@ -52,6 +61,7 @@ typedef struct {
     int *row_node_id, *pre_off, *out_off, *row_remain, *pre_idx, *out_idx;
     int use_remain;              /* abpt->wb >= 0 || abpt->zdrop > 0 */
     int m;                       /* alphabet size: bounds the aligned-pool pre-check */
+    int serial_fold;             /* 1: lane-0 mutation walk (ABPOA_AMD_SERIAL_FOLD) */
     abamd_fold_out_t *out;
 } abamd_fold_round_job_t;
 

@@ -14,10 +14,12 @@
  *     stays on the GPU.
  *
  * Mutation semantics match abpoa_add_graph_alignment (abpoa_graph.c:689-774)
- * + abpoa_topological_sort (:322-357); the serial passes run on lane 0 (the
- * graph walk is pointer-chasing over an L2-resident working set; cross-set
- * parallelism — one workgroup per read set, hundreds of sets per launch —
- * fills the chip).
+ * + abpoa_topological_sort (:322-357). The production kernel runs the
+ * mutation walk across its 64 lanes (abamd_fold_par.inc: the walk is a chain
+ * of dependent cache misses per CIGAR op, so the lanes overlap the misses;
+ * slot order comes from prefix sums); the Kahn BFS, whose queue order is the
+ * topological index, stays on lane 0. Cross-set parallelism — one workgroup
+ * per read set, hundreds of sets per launch — fills the chip.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,10 +43,14 @@ typedef uint64_t abpoa_cigar_t;
 #define ABAMD_FC_FN __device__
 #define ABAMD_FC_FAIL(msg) do { abort(); } while (0)
 #define ABAMD_FC_FAIL_RET(val, msg) do { abort(); } while (0)
-#include "abamd_fold_core.inc"
-/* consensus body: the phases synchronise the workgroup between them; the
- * queue-based witness (double pow/log10 phred) is host-only */
+/* phased bodies synchronise the workgroup between their phases */
 #define ABAMD_FC_BARRIER() __syncthreads()
+#include "abamd_fold_core.inc"
+/* lane-parallel mutation walk: range-checked and bounded, never aborts */
+#define ABAMD_FC_ROLLED _Pragma("unroll 1")
+#include "abamd_fold_par.inc"
+/* consensus body; the queue-based witness (double pow/log10 phred) is
+ * host-only */
 #define ABAMD_CONS_PHASED_ONLY
 #include "abamd_cons_core.inc"
 /* row-column MSA body: bounded and range-checked throughout, never aborts */
@@ -84,6 +90,65 @@ extern "C" __global__ void abamd_fold_kernel(fold_job_t *jobs, int n_jobs) {
     }
 }
 
+/* Validation kernel for the lane-parallel walk (abamd_fold_gpu_test.cpp -p):
+ * the same job as abamd_fold_kernel plus the walk's scratch; the walk runs
+ * across the wave, a tripped check is counted in *fallbacks and redone on
+ * lane 0, the derived passes follow serially as above. LDS: 384 ints. */
+typedef struct {
+    fold_job_t j;
+    int *owner, *path, *nsp, *opres, *e_in, *e_out; /* ws_cap ints each */
+    int ws_cap;
+    int *fallbacks;
+} fold_par_job_t;
+
+extern "C" __global__ __launch_bounds__(64)
+void abamd_fold_par_kernel(fold_par_job_t *jobs, int n_jobs) {
+    __shared__ int part[ABAMD_PAR_PARTS * 64];
+    int j = blockIdx.x;
+    if (j >= n_jobs) return;
+    fold_par_job_t *pj = &jobs[j];
+    fold_job_t *job = &pj->j;
+    flat_graph_t gl = job->g; /* by value, as in the production kernel */
+    flat_par_ws_t ws;
+    ws.owner = pj->owner; ws.path = pj->path; ws.nsp = pj->nsp; ws.opres = pj->opres;
+    ws.e_in = pj->e_in; ws.e_out = pj->e_out; ws.cap = pj->ws_cap;
+    ws.part = part; ws.part_cap = ABAMD_PAR_PARTS * 64;
+    const int ok = abamd_flat_apply_par(&gl, ABPOA_SRC_NODE_ID, ABPOA_SINK_NODE_ID,
+                                        job->seq, job->weight, job->seq_l, job->qpos_to_node_id,
+                                        job->n_cigar, job->cigar, job->read_id,
+                                        job->add_read_id, 1, &ws, (int)threadIdx.x, 64);
+    __syncthreads();
+    if (!ok) {
+        if (threadIdx.x == 0) {
+            *pj->fallbacks += 1;
+            abamd_flat_apply_alignment(&gl, ABPOA_SRC_NODE_ID, ABPOA_SINK_NODE_ID,
+                                       job->seq, job->weight, job->seq_l, job->qpos_to_node_id,
+                                       job->n_cigar, job->cigar, job->read_id,
+                                       job->add_read_id, 1);
+            job->g.node_n = gl.node_n;
+            job->g.edge_n_in = gl.edge_n_in; job->g.edge_n_out = gl.edge_n_out;
+            job->g.aln_n = gl.aln_n;
+        }
+        __syncthreads();
+        gl.node_n = job->g.node_n;
+        gl.edge_n_in = job->g.edge_n_in; gl.edge_n_out = job->g.edge_n_out;
+        gl.aln_n = job->g.aln_n;
+    }
+    if (threadIdx.x == 0) {
+        job->g.node_n = gl.node_n;
+        job->g.edge_n_in = gl.edge_n_in; job->g.edge_n_out = gl.edge_n_out;
+        job->g.aln_n = gl.aln_n;
+        abamd_flat_topo_index(&gl, job->index_to_node_id, job->node_id_to_index,
+                              job->scratch);
+        abamd_flat_sort_adjacency(&gl);
+        abamd_flat_remain(&gl, job->max_remain, job->scratch);
+        abamd_flat_update_n_span(&gl, job->index_to_node_id,
+                                 job->node_id_to_index, 1);
+        if (job->msa_rank)
+            abamd_flat_msa_rank(&gl, job->msa_rank, job->scratch);
+    }
+}
+
 #ifdef ABAMD_KPROF
 __device__ unsigned long long abamd_kprof_fold[16];
 extern "C" void abamd_kprof_fold_fetch(unsigned long long *out) {
@@ -103,10 +168,10 @@ extern "C" void abamd_kprof_fold_reset(void) {
 /* ------------------------------------------------------------------ */
 /* Wave-parallel variants of the order-insensitive derived passes.     */
 /*                                                                     */
-/* The mutation (apply) and the Kahn BFS stay serial on lane 0 — their */
-/* ORDER is observable (queue order defines the topo index; the fold   */
-/* order defines edge append order). Everything else is a pure         */
-/* function of the graph whose outputs the serial twin provably        */
+/* The Kahn BFS stays serial on lane 0: its queue order defines the    */
+/* topo index. (The mutation walk's order is observable too, but it is */
+/* reproduced by prefix sums: abamd_fold_par.inc.) Everything else is  */
+/* a pure function of the graph whose outputs the serial twin provably */
 /* produces; these versions compute the same values with all 64 lanes  */
 /* (per-node independence, wave prefix scans), cutting the per-set     */
 /* fold latency that otherwise matches the DP kernel's whole wall.     */
@@ -338,6 +403,7 @@ __device__ static int dev_par_build_rows(const flat_graph_t *fg,
 
 extern "C" __global__ __launch_bounds__(64)
 void abamd_fold_round_kernel(abamd_fold_round_job_t *jobs, int n_jobs) {
+    __shared__ int par_part[ABAMD_PAR_PARTS * FOLD_WAVE];
     const int j = blockIdx.x;
     if (j >= n_jobs) return;
     abamd_fold_round_job_t *job = &jobs[j];
@@ -412,22 +478,46 @@ void abamd_fold_round_kernel(abamd_fold_round_job_t *jobs, int n_jobs) {
     __syncthreads();
 
     FKPROF_T(ft0);
-    if (lane == 0) {
-        abamd_flat_apply_alignment(g, ABPOA_SRC_NODE_ID, ABPOA_SINK_NODE_ID,
-                                   job->seq, job->weight, job->seq_l, NULL,
-                                   n_cigar, job->cigar, job->read_id,
-                                   job->add_read_id, 1);
-        /* publish the mutated counters so every lane's local copy agrees */
-        job->g.node_n = gl.node_n;
-        job->g.edge_n_in = gl.edge_n_in;
-        job->g.edge_n_out = gl.edge_n_out;
-        job->g.aln_n = gl.aln_n;
+    /* Mutation walk across the wave (abamd_fold_par.inc). Its scratch is
+     * what is dead right now: `scratch` (owner, path) and the previous
+     * round's CSR arrays, which dev_par_build_rows rewrites below — the
+     * early returns above keep that CSR intact. Each is >= node_cap ints, and
+     * node_cap >= node_n + seq_l + 2 (pre-check) covers seq_l + 1 path edges;
+     * a CIGAR longer than node_cap takes the serial walk. Every lane ends
+     * with the same counters in its own gl. */
+    int walk = ABAMD_FOLD_WALK_SERIAL;
+    if (!job->serial_fold) {
+        flat_par_ws_t ws;
+        ws.owner = job->scratch; ws.path = job->scratch + g->node_cap;
+        ws.opres = job->row_node_id; ws.nsp = job->row_remain;
+        ws.e_in = job->pre_off; ws.e_out = job->out_off;
+        ws.cap = g->node_cap;
+        ws.part = par_part; ws.part_cap = ABAMD_PAR_PARTS * FOLD_WAVE;
+        walk = abamd_flat_apply_par(g, ABPOA_SRC_NODE_ID, ABPOA_SINK_NODE_ID,
+                                    job->seq, job->weight, job->seq_l, NULL,
+                                    n_cigar, job->cigar, job->read_id,
+                                    job->add_read_id, 1, &ws, lane, FOLD_WAVE)
+               ? ABAMD_FOLD_WALK_PARALLEL : ABAMD_FOLD_WALK_FALLBACK;
+        __syncthreads();
     }
-    __syncthreads();
-    gl.node_n = job->g.node_n;
-    gl.edge_n_in = job->g.edge_n_in;
-    gl.edge_n_out = job->g.edge_n_out;
-    gl.aln_n = job->g.aln_n;
+    if (walk != ABAMD_FOLD_WALK_PARALLEL) {
+        if (lane == 0) {
+            abamd_flat_apply_alignment(g, ABPOA_SRC_NODE_ID, ABPOA_SINK_NODE_ID,
+                                       job->seq, job->weight, job->seq_l, NULL,
+                                       n_cigar, job->cigar, job->read_id,
+                                       job->add_read_id, 1);
+            /* publish the mutated counters so every lane's local copy agrees */
+            job->g.node_n = gl.node_n;
+            job->g.edge_n_in = gl.edge_n_in;
+            job->g.edge_n_out = gl.edge_n_out;
+            job->g.aln_n = gl.aln_n;
+        }
+        __syncthreads();
+        gl.node_n = job->g.node_n;
+        gl.edge_n_in = job->g.edge_n_in;
+        gl.edge_n_out = job->g.edge_n_out;
+        gl.aln_n = job->g.aln_n;
+    }
     FKPROF_T(ft1);
     FKPROF_ACC(1, ft0, ft1);
     dev_par_in_deg(g, job->scratch, lane);
@@ -479,6 +569,7 @@ void abamd_fold_round_kernel(abamd_fold_round_job_t *jobs, int n_jobs) {
         o->n_rows = n_rows;
         o->n_pre = job->pre_off[n_rows];
         o->n_out = job->out_off[n_rows];
+        o->walk = walk;
     }
 }
 

@@ -58,6 +58,14 @@ void abpoa_amd_get_msa_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_
     if (kernel_ns) *kernel_ns = 0;
 }
 void abpoa_amd_reset_msa_stats(void) {}
+/* nor a device fold */
+void abpoa_amd_get_fold_stats(uint64_t *parallel_folds, uint64_t *fallback_folds,
+                              uint64_t *serial_folds) {
+    if (parallel_folds) *parallel_folds = 0;
+    if (fallback_folds) *fallback_folds = 0;
+    if (serial_folds) *serial_folds = 0;
+}
+void abpoa_amd_reset_fold_stats(void) {}
 void abamd_timing_report(const char *tag) { (void)tag; }
 
 static abamd_batch_job_t *stub_slot_batch[8];

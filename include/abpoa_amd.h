@@ -280,6 +280,29 @@ void abpoa_amd_get_msa_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_
                              uint64_t *d2h_bytes, uint64_t *kernel_ns);
 void abpoa_amd_reset_msa_stats(void);
 
+/* Graph-fold stage of the batched device-resident driver. Each read of each
+ * set is folded into the set's graph by one fold kernel job; the graph
+ * mutation walk inside it runs across the job's 64 lanes (abamd_fold_par.inc).
+ * The walk checks its own assumptions (one visit per node and per aligned
+ * group, ids in range, bounded chains); a job in which a check fails leaves
+ * the graph untouched and repeats the walk with the serial single-lane code,
+ * so outputs never depend on the path. Setting the environment variable
+ * ABPOA_AMD_SERIAL_FOLD (any value; read on every batch call) makes every job
+ * use the single-lane walk — outputs are identical, it exists for A/B
+ * measurement.
+ *
+ * Counters are cumulative since the last reset:
+ *   parallel_folds  fold jobs whose walk ran on the lane-parallel path
+ *   fallback_folds  fold jobs whose lane-parallel walk tripped a check and
+ *                   was redone serially (expected: 0)
+ *   serial_folds    fold jobs that ran the single-lane walk on request
+ * Jobs that fold nothing (failed DP, pool overflow before the relaunch, empty
+ * alignment) are not counted. Any pointer may be NULL. Builds without the GPU
+ * core report zeros. */
+void abpoa_amd_get_fold_stats(uint64_t *parallel_folds, uint64_t *fallback_folds,
+                              uint64_t *serial_folds);
+void abpoa_amd_reset_fold_stats(void);
+
 #ifdef __cplusplus
 }
 #endif
