@@ -333,6 +333,7 @@ static int64_t pack_job(HostBuf &hb, JobPack &P, abpoa_t *ab, abpoa_para_t *abpt
     jb.inc_path_score = abpt->inc_path_score;
     jb.node_n_init = g->node_n;
     jb.ret_cigar = abpt->ret_cigar;
+    jb.dp_ring = abamd_dp_ring_depth();
 
     /* arena demand estimate: adaptive bands are ~2w + drift; reserve slack */
     int64_t est = (int64_t)n_rows * (2 * (int64_t)jb.w + 160) + qlen + 64;

@@ -296,6 +296,7 @@ struct Batch {
     int n_sets = 0, n_groups = 3;
     int use_remain = 0, planes = 5;
     int serial_fold = 0;         /* ABPOA_AMD_SERIAL_FOLD: lane-0 mutation walk */
+    int dp_ring = ABAMD_DP_RING_MAX; /* ABPOA_AMD_DP_RING: DP kernel LDS ring depth */
     double budget_bytes = 0;
     uint64_t retry_jobs = 0, pool_expands = 0;
     double t_host_build = 0, t_finish = 0;
@@ -369,6 +370,7 @@ void build_jobs(Batch &B, Slot &S, const std::vector<int> &set_list, int r,
         jb.inc_path_score = 0;
         jb.node_n_init = st.g.node_n;
         jb.ret_cigar = 1;
+        jb.dp_ring = B.dp_ring;
         jb.mat = (const int*)g_ctx.d_mat.p;
 
         abamd_fold_round_job_t &fj = S.hfjobs[i];
@@ -1120,6 +1122,7 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     B.n_sets = n_sets;
     B.use_remain = (abpt->wb >= 0 || abpt->zdrop > 0);
     B.serial_fold = getenv("ABPOA_AMD_SERIAL_FOLD") ? 1 : 0;
+    B.dp_ring = abamd_dp_ring_depth();
     B.planes = abpt->gap_mode == ABPOA_CONVEX_GAP ? 3 /* F recomputed at backtrack */
              : abpt->gap_mode == ABPOA_AFFINE_GAP ? 3 : 1;
     B.sets.resize(n_sets);

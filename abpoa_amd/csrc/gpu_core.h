@@ -72,8 +72,17 @@ typedef struct {
     int zdrop, inc_path_score;
     int node_n_init;             /* graph node_n: initial value of max_left */
     int ret_cigar;
+    int dp_ring;                 /* convex multi-wave kernel: predecessors up to
+                                    this many rows back are gathered from the
+                                    LDS row ring (abamd_dp_ring_depth(); 1 =
+                                    previous row only) */
     const int *mat;              /* [m*m] scoring matrix */
 } abamd_gpu_job_t;
+
+/* Rows of look-back the convex multi-wave kernel serves from its LDS ring. */
+#define ABAMD_DP_RING_MAX 10
+/* ABPOA_AMD_DP_RING, clamped to 1..ABAMD_DP_RING_MAX (unset: the maximum) */
+int abamd_dp_ring_depth(void);
 
 typedef struct {
     int32_t best_score;

@@ -3,12 +3,13 @@
  * One wavefront (64 lanes) per alignment job, 4 jobs per 256-thread
  * workgroup. The wave sweeps the graph's topologically-sorted rows; within a
  * row the band is processed in 64-cell register chunks:
- *   - M/E gather from predecessor rows. The common predecessor (in-degree is
- *     ~1.05) is the immediately preceding row, whose H/E planes are kept in a
- *     double-buffered LDS cache (BMAX cells) — a ~50-cycle LDS read
- *     replaces a ~900-cycle HBM round-trip on the row-to-row dependent chain.
- *     Other predecessors (and bands wider than the cache) read the banded
- *     HBM arena with coalesced 2/4-byte loads.
+ *   - M/E gather from predecessor rows. The immediately preceding row's H/E
+ *     planes are kept in a double-buffered LDS cache (BMAX cells) — a
+ *     ~50-cycle LDS read replaces a ~900-cycle HBM round-trip on the
+ *     row-to-row dependent chain. Other predecessors (and bands wider than
+ *     the cache) read the banded HBM arena with coalesced 2/4-byte loads.
+ *     (r-1 is the only predecessor for the first reads of a set only; the
+ *     convex multi-wave kernel below keeps a ring of recent rows instead.)
  *   - the F (insertion) recurrence is a wavefront max-plus log-scan
  *     (__shfl_up, 6 doubling steps) with a sequential carry between chunks,
  *   - the banded planes stream to the HBM arena with coalesced stores
@@ -36,12 +37,18 @@
  * row-loop phase of the convex kernel across all jobs. Diagnostic build
  * only — never part of the product library. */
 #ifdef ABAMD_KPROF
-__device__ unsigned long long abamd_kprof_acc[16];
+/* slots 0..15: phase totals; 16..30: the convex multi-wave kernel's rows by
+ * class (0 = one predecessor r-1 in the ring, 1 = all predecessors in the
+ * ring, 2 = at least one arena gather): rows 16+c, gather+hpre cycles 19+c,
+ * epilogue cycles 22+c, row cycles 25+c; 28 rows wider than a ring slot,
+ * 29 rows with more than MW_NPF predecessors, 30 predecessor references */
+#define ABAMD_KPROF_N 32
+__device__ unsigned long long abamd_kprof_acc[ABAMD_KPROF_N];
 extern "C" void abamd_kprof_fetch(unsigned long long *out) {
     (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(abamd_kprof_acc), sizeof(abamd_kprof_acc));
 }
 extern "C" void abamd_kprof_reset(void) {
-    unsigned long long z[16] = {0};
+    unsigned long long z[ABAMD_KPROF_N] = {0};
     (void)hipMemcpyToSymbol(HIP_SYMBOL(abamd_kprof_acc), z, sizeof(z));
 }
 #define KPROF_T(v) unsigned long long v = __builtin_readcyclecounter()
@@ -155,13 +162,47 @@ __device__ static int dev_push_cigar(uint64_t *cig, int *n_c, int cap, int op, i
 /* associative and the inf_min headroom (+512*ext_max, the same bound   */
 /* the one-wave scan relies on) keeps every comparison un-wrapped.      */
 /* Three block barriers per row replace ~5 serial chunk iterations.     */
+/*                                                                      */
+/* Row ring. Only the first few reads see a chain-like graph: after     */
+/* read 10 of a 50 x 10 kbp set 60 % of the rows have a predecessor     */
+/* that is not row r-1, after read 50 it is 91 % (the Kahn BFS          */
+/* interleaves the variant branches), but 99 % of those references      */
+/* reach back at most 10 rows. So the H/E1/E2 bands of the last         */
+/* MW_RING rows stay in LDS, slot = row % MW_RING, with a               */
+/* {row, beg, end} entry per slot (row = -1 when the band was wider     */
+/* than a slot). A predecessor p with r - p <= dp_ring and a valid slot */
+/* is gathered from LDS and gives its band start from the slot table;   */
+/* anything else reads row_meta and the arena. Every value in the ring  */
+/* is the value the arena holds, so the switch (job field dp_ring, 1 =  */
+/* previous row only) does not change a single cell.                    */
+/* Ordering: row r writes only slot r % MW_RING, data and table entry,  */
+/* after its barrier B2. That slot held row r - MW_RING; the oldest row */
+/* anyone still reads is r - MW_RING + 1 (by row r itself, before B1),  */
+/* and rows < r finished their gathers before their own B1. B3 orders   */
+/* the writes before row r+1's reads. The first three predecessors of a */
+/* row are rolled one row ahead like the other row scalars; their ring  */
+/* or row_meta lookups are done once per row and shared by the band     */
+/* start (min_pre_beg) and the gather.                                  */
 /* ------------------------------------------------------------------ */
 #define MWAVES 8
 #define MWT (WAVE * MWAVES)
-#define BMW 512 /* prev-row LDS cache width (cells); wider bands re-read the arena */
+#define BMW 512 /* ring slot width (cells); wider bands re-read the arena */
+/* ring slots: rows r-1 .. r-ABAMD_DP_RING_MAX are readable while row r is
+ * written. int32: 11 x 3 x 512 x 4 B = 66 KiB (+3 KiB matrix), under the
+ * 80 KiB that keeps two blocks per CU; int16 takes half. Depth 10 is where
+ * one more slot adds less than one point of coverage after read 50
+ * (d<=8 96.9 %, d<=10 99.1 %, d<=12 99.75 % of the far references). */
+#define MW_RING (ABAMD_DP_RING_MAX + 1)
+/* predecessors (and out-edges) per row rolled one row ahead: 3 keeps the
+ * int32 instantiation at 104 VGPRs, which leaves a fold wave (72) room on a
+ * SIMD next to four DP waves; 4 costs 106 (112 allocated) */
+#define MW_NPF 3
+
+/* one predecessor row as the gather sees it: slot >= 0 -> LDS ring */
+struct mw_pred_t { int slot, beg, end; };
 
 template <typename S>
-__global__ __launch_bounds__(MWT, 1)
+__global__ __launch_bounds__(MWT, 4) /* 4 waves/SIMD: two blocks per CU */
 void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
                          abamd_gpu_res_t *__restrict__ results, int n_jobs) {
     const int jid = blockIdx.x;
@@ -170,7 +211,8 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
     const int wv = tid / WAVE, lane = tid % WAVE;
 
     __shared__ int mat_lds[27 * 27];
-    __shared__ S prev_lds[2][3 * BMW];
+    __shared__ S ring_lds[MW_RING][3 * BMW];
+    __shared__ int4 ring_tbl[MW_RING]; /* {row or -1, beg, end, 0} per slot */
     __shared__ S sc_h[MWAVES], sc_f1[MWAVES], sc_f2[MWAVES];
     __shared__ int sc_red[3 * MWAVES];
     __shared__ S sc_carry[3];
@@ -190,42 +232,68 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
     const int end_remain = jb.max_remain[n_rows - 1];
     S *arena = (S*)jb.arena;
     const uint8_t *__restrict__ query = jb.query;
+    /* The job's arrays again as global-address-space pointers for the row
+     * loop. Pointers loaded from the job struct are generic, and generic
+     * (flat) loads and stores count on the LDS counter as well: every LDS
+     * wait of a row, the first ring read included, then also waited for the
+     * rolled global loads issued just above it and for the previous row's
+     * plane stores. */
+    typedef __attribute__((address_space(1))) S GS;
+    typedef __attribute__((address_space(1))) int gint_t;
+    typedef __attribute__((address_space(1))) uint8_t gu8_t;
+    typedef __attribute__((address_space(1))) abamd_row_meta_t gmeta_t;
+    GS *const g_arena = (GS*)jb.arena;
+    const gu8_t *const g_query = (const gu8_t*)jb.query;
+    const gu8_t *const g_row_base = (const gu8_t*)jb.row_base;
+    const gint_t *const g_pre_off = (const gint_t*)jb.pre_off;
+    const gint_t *const g_pre_idx = (const gint_t*)jb.pre_idx;
+    const gint_t *const g_pre_ps = (const gint_t*)jb.pre_ps;
+    const gint_t *const g_out_off = (const gint_t*)jb.out_off;
+    const gint_t *const g_out_idx = (const gint_t*)jb.out_idx;
+    const gint_t *const g_max_remain = (const gint_t*)jb.max_remain;
+    gint_t *const g_max_left = (gint_t*)jb.max_left;
+    gint_t *const g_max_right = (gint_t*)jb.max_right;
+    gmeta_t *const g_meta = (gmeta_t*)jb.row_meta;
 
     for (int i = tid; i < m * m; i += MWT) mat_lds[i] = jb.mat[i];
     if (tid == 0) { res->status = ABAMD_JOB_OK; res->n_cigar = 0; }
 
     /* adaptive band state init (abpoa_topological_sort:347-353 + first_dp) */
     for (int i = tid; i < n_rows; i += MWT) {
-        jb.max_left[i] = jb.node_n_init;
-        jb.max_right[i] = 0;
+        g_max_left[i] = jb.node_n_init;
+        g_max_right[i] = 0;
     }
-    if (tid == 0) { jb.max_left[0] = 0; jb.max_right[0] = 0; }
-    for (int k = jb.out_off[0] + tid; k < jb.out_off[1]; k += MWT) {
-        int o = jb.out_idx[k];
-        jb.max_left[o] = 1; jb.max_right[o] = 1;
+    if (tid == 0) { g_max_left[0] = 0; g_max_right[0] = 0; }
+    for (int k = g_out_off[0] + tid; k < g_out_off[1]; k += MWT) {
+        int o = g_out_idx[k];
+        g_max_left[o] = 1; g_max_right[o] = 1;
     }
+    if (tid < MW_RING) ring_tbl[tid] = make_int4(-1, 0, -1, 0);
     __syncthreads();
 
-    int buf_cur = 0;
-    int prev_ok = 0, prev_row = -1, prev_beg = 0, prev_end = -1;
+    const int depth = jb.dp_ring < 1 ? 1
+                    : (jb.dp_ring > ABAMD_DP_RING_MAX ? ABAMD_DP_RING_MAX : jb.dp_ring);
+    const int ips = jb.inc_path_score;
+    const int pre_last = g_pre_off[n_rows] - 1; /* clamps for the rolled loads */
+    const int out_last = g_out_off[n_rows] - 1;
 
     /* ---- first row (simd_abpoa_cg_first_dp) ---- */
     int64_t used;
     {
-        int mr = jb.max_remain[0] - end_remain - 1;
+        int mr = g_max_remain[0] - end_remain - 1;
         int end0;
         if (jb.banded) {
-            int t = jb.max_right[0] > qlen - mr ? jb.max_right[0] : qlen - mr;
+            int t = g_max_right[0] > qlen - mr ? g_max_right[0] : qlen - mr;
             end0 = (qlen < t + w) ? qlen : t + w;
         } else end0 = qlen;
-        if (tid == 0) { meta[0].beg = 0; meta[0].end = end0; meta[0].off = 0; }
+        if (tid == 0) { g_meta[0].beg = 0; g_meta[0].end = end0; g_meta[0].off = 0; }
         int64_t bw = end0 + 1;
         used = bw;
         /* 3 planes only (H,E1,E2): the F planes are recomputed from stored H
          * at backtrack time (validated: tools/f_recompute_experiment.py — a
          * 40% cut of plane bytes and arena capacity) */
-        S *H = arena, *E1 = arena + bw, *E2 = arena + 2 * bw;
-        S *c = &prev_lds[buf_cur][0];
+        GS *H = g_arena, *E1 = g_arena + bw, *E2 = g_arena + 2 * bw;
+        S *c = &ring_lds[0][0];
         const int fits = end0 + 1 <= BMW;
         for (int j = tid; j <= end0; j += MWT) {
             S hv, e1v2, e2v2;
@@ -244,8 +312,7 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
                 c[j] = hv; c[BMW + j] = e1v2; c[2 * BMW + j] = e2v2;
             }
         }
-        if (fits) { prev_ok = 1; prev_row = 0; prev_beg = 0; prev_end = end0; }
-        buf_cur ^= 1;
+        if (tid == 0) ring_tbl[0] = make_int4(fits ? 0 : -1, 0, end0, 0);
         __syncthreads();
     }
 
@@ -254,40 +321,128 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
      * same copy, and skip-edge pushes are idempotent same-value writes
      * done by every thread so each thread's later prefetch of the pushed
      * row is self-ordered) ---- */
-    int cur_pk0 = jb.pre_off[1];
-    int cur_pk1 = jb.pre_off[2 <= n_rows ? 2 : n_rows];
-    int cur_oo0 = jb.out_off[1];
-    int cur_oo1 = jb.out_off[2 <= n_rows ? 2 : n_rows];
-    int cur_remain = jb.max_remain[1];
-    int cur_ml_mem = jb.max_left[1];
-    int cur_mr_mem = jb.max_right[1];
-    int cur_pidx0 = jb.pre_idx[cur_pk0];
-    int cur_ps0 = jb.pre_ps[cur_pk0];
+    int cur_pk0 = g_pre_off[1];
+    int cur_pk1 = g_pre_off[2 <= n_rows ? 2 : n_rows];
+    int cur_oo0 = g_out_off[1];
+    int cur_oo1 = g_out_off[2 <= n_rows ? 2 : n_rows];
+    int cur_remain = g_max_remain[1];
+    int cur_ml_mem = g_max_left[1];
+    int cur_mr_mem = g_max_right[1];
+    /* the first MW_NPF predecessor indices, loaded unconditionally (index
+     * clamped into the array) so they do not wait for the row's pre_off */
+    int cur_pidx[MW_NPF];
+    #pragma unroll
+    for (int i = 0; i < MW_NPF; ++i) {
+        int k = cur_pk0 + i; if (k > pre_last) k = pre_last; if (k < 0) k = 0;
+        cur_pidx[i] = g_pre_idx[k];
+    }
+    int cur_oidx[MW_NPF];
+    #pragma unroll
+    for (int i = 0; i < MW_NPF; ++i) {
+        int k = cur_oo0 + i; if (k > out_last) k = out_last; if (k < 0) k = 0;
+        cur_oidx[i] = g_out_idx[k];
+    }
+    int cur_base = g_row_base[1];
     int push_ml = 0x7fffffff, push_mr = -0x7fffffff;
+    int slot = 0; /* r % MW_RING */
 #ifdef ABAMD_KPROF
     unsigned long long mw_a = 0, mw_b = 0, mw_c = 0, mw_d = 0, mw_rows = 0;
 #endif
     for (int r = 1; r < n_rows - 1; ++r) {
         KPROF_T(mt0);
+        if (++slot == MW_RING) slot = 0;
         const int pk0 = cur_pk0, pk1 = cur_pk1;
         const int oo0 = cur_oo0, oo1 = cur_oo1;
         const int row_remain = cur_remain;
-        const int pidx0 = cur_pidx0;
-        const S ps0 = (S)cur_ps0;
+        int pidx[MW_NPF], oidx[MW_NPF];
+        #pragma unroll
+        for (int i = 0; i < MW_NPF; ++i) {
+            pidx[i] = __builtin_amdgcn_readfirstlane(cur_pidx[i]);
+            oidx[i] = __builtin_amdgcn_readfirstlane(cur_oidx[i]);
+        }
+        const int base = cur_base;
         const int ml_eff = cur_ml_mem < push_ml ? cur_ml_mem : push_ml;
         const int mr_eff = cur_mr_mem > push_mr ? cur_mr_mem : push_mr;
         {
             const int nr = r + 1;
             cur_pk0 = pk1;
-            cur_pk1 = jb.pre_off[nr + 1];
+            cur_pk1 = g_pre_off[nr + 1];
             cur_oo0 = oo1;
-            cur_oo1 = jb.out_off[nr + 1];
-            cur_remain = jb.max_remain[nr];
-            cur_ml_mem = jb.max_left[nr];
-            cur_mr_mem = jb.max_right[nr];
-            cur_pidx0 = jb.pre_idx[cur_pk0];
-            cur_ps0 = jb.pre_ps[cur_pk0];
+            cur_oo1 = g_out_off[nr + 1];
+            cur_remain = g_max_remain[nr];
+            cur_ml_mem = g_max_left[nr];
+            cur_mr_mem = g_max_right[nr];
+            cur_base = g_row_base[nr];
+            #pragma unroll
+            for (int i = 0; i < MW_NPF; ++i) {
+                int k = cur_pk0 + i; if (k > pre_last) k = pre_last; if (k < 0) k = 0;
+                cur_pidx[i] = g_pre_idx[k];
+                k = cur_oo0 + i; if (k > out_last) k = out_last; if (k < 0) k = 0;
+                cur_oidx[i] = g_out_idx[k];
+            }
         }
+        /* predecessor lookup: ring slot table first (one LDS read), else
+         * row_meta. Uniform across the block; readfirstlane keeps the
+         * results in scalar registers. */
+        const int npre = pk1 - pk0;
+        auto ring_probe = [&](int p, int4 &t) -> int { /* slot index to test */
+            const int d = r - p;
+            int s = slot - ((d >= 1 && d <= ABAMD_DP_RING_MAX) ? d : 0);
+            if (s < 0) s += MW_RING;
+            t = ring_tbl[s];
+            return s;
+        };
+        auto pred_resolve = [&](int p, int s, const int4 &t, mw_pred_t &q) {
+            const int d = r - p;
+            if (d >= 1 && d <= depth && __builtin_amdgcn_readfirstlane(t.x) == p) {
+                q.slot = s;
+                q.beg = __builtin_amdgcn_readfirstlane(t.y);
+                q.end = __builtin_amdgcn_readfirstlane(t.z);
+            } else { /* rare: the gather re-reads row_meta for end and offset */
+                q.slot = -1;
+                q.beg = __builtin_amdgcn_readfirstlane(g_meta[p].beg);
+                q.end = -1;
+            }
+        };
+        mw_pred_t pf[MW_NPF];
+        int min_pre_beg = 0x7fffffff;
+        {
+            int4 pt[MW_NPF]; int psl[MW_NPF];
+            #pragma unroll
+            for (int i = 0; i < MW_NPF; ++i) psl[i] = ring_probe(pidx[i], pt[i]);
+            #pragma unroll
+            for (int i = 0; i < MW_NPF; ++i) {
+                pf[i].slot = -1; pf[i].beg = 0; pf[i].end = -1;
+                if (i < npre) {
+                    pred_resolve(pidx[i], psl[i], pt[i], pf[i]);
+                    if (pf[i].beg < min_pre_beg) min_pre_beg = pf[i].beg;
+                }
+            }
+            for (int k = pk0 + MW_NPF; k < pk1; ++k) {
+                const int p = g_pre_idx[k];
+                int4 t; mw_pred_t q;
+                const int s = ring_probe(p, t);
+                pred_resolve(p, s, t, q);
+                if (q.beg < min_pre_beg) min_pre_beg = q.beg;
+            }
+        }
+#ifdef ABAMD_KPROF
+        /* row class by what a full-depth ring would serve, whatever dp_ring
+         * is: 0 = single predecessor r-1 in the ring, 1 = every predecessor
+         * in the ring, 2 = at least one arena gather */
+        int kp_cls;
+        unsigned long long kp_a = 0;
+        {
+            int n_far = 0;
+            for (int k = pk0; k < pk1; ++k) {
+                const int p = g_pre_idx[k];
+                int4 t; (void)ring_probe(p, t);
+                const int d = r - p;
+                if (!(d >= 1 && d <= ABAMD_DP_RING_MAX && t.x == p)) ++n_far;
+            }
+            kp_cls = n_far ? 2 : ((npre == 1 && pidx[0] == r - 1) ? 0 : 1);
+        }
+#endif
         int beg, end;
         {
             int mr = row_remain - end_remain - 1;
@@ -296,32 +451,18 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
                 beg = lo - w; if (beg < 0) beg = 0;
                 int hi = mr_eff > qlen - mr ? mr_eff : qlen - mr;
                 end = hi + w; if (end > qlen) end = qlen;
-                int min_pre_beg;
-                if (pk1 - pk0 == 1) {
-                    min_pre_beg = (prev_ok && pidx0 == prev_row) ? prev_beg : meta[pidx0].beg;
-                } else {
-                    min_pre_beg = 0x7fffffff;
-                    for (int k = pk0; k < pk1; ++k) {
-                        const int pidx = jb.pre_idx[k];
-                        int pb = (prev_ok && pidx == prev_row) ? prev_beg : meta[pidx].beg;
-                        if (pb < min_pre_beg) min_pre_beg = pb;
-                    }
-                }
                 if (beg < min_pre_beg) beg = min_pre_beg;
             } else { beg = 0; end = qlen; }
         }
         const int64_t bw = end - beg + 1;
         if (used + bw > jb.arena_cap) { if (tid == 0) res->status = ABAMD_JOB_ARENA_OVERFLOW; return; }
         const int64_t off = used;
-        if (tid == 0) { meta[r].beg = beg; meta[r].end = end; meta[r].off = off; }
+        if (tid == 0) { g_meta[r].beg = beg; g_meta[r].end = end; g_meta[r].off = off; }
         used += bw;
-        S *H = arena + off * 3, *E1r = H + bw, *E2r = E1r + bw;
-        const uint8_t base = jb.row_base[r];
+        GS *H = g_arena + off * 3, *E1r = H + bw, *E2r = E1r + bw;
         const int *mrow = &mat_lds[base * m];
         const int cache_fits = bw <= BMW;
-        S *cw = &prev_lds[buf_cur][0];
-        const S *cr = &prev_lds[buf_cur ^ 1][0];
-        const bool fast1 = (pk1 - pk0 == 1) && prev_ok && (pidx0 == prev_row);
+        S *cw = &ring_lds[slot][0];
 
         S carry_h = inf_min, f1c = inf_min, f2c = inf_min; /* superchunk carries */
         S lmax = inf_min; int lleft = -1, lright = -1;
@@ -330,44 +471,30 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             const int j = ss + tid;
             const bool act = j <= end;
             S h = inf_min, e1v = inf_min, e2v = inf_min;
-            if (fast1) {
-                if (act) {
-                    if (local_mode && j == 0) { if (ps0 > h) h = ps0; }
-                    if (j - 1 >= prev_beg && j - 1 <= prev_end) {
-                        S v = (S)(cr[j - 1 - prev_beg] + ps0);
-                        if (v > h) h = v;
-                    }
-                    if (j >= prev_beg && j <= prev_end) {
-                        S v1 = (S)(cr[BMW + j - prev_beg] + ps0);
-                        S v2 = (S)(cr[2 * BMW + j - prev_beg] + ps0);
-                        if (v1 > e1v) e1v = v1;
-                        if (v2 > e2v) e2v = v2;
-                    }
-                }
-            } else for (int k = pk0; k < pk1; ++k) {
-                const int p = jb.pre_idx[k];
-                const S ps = (S)jb.pre_ps[k];
-                if (prev_ok && p == prev_row) {
+            auto gather = [&](const int p, const mw_pred_t &q, const S ps) {
+                if (q.slot >= 0) {
+                    const S *cr = &ring_lds[q.slot][0];
                     if (act) {
                         if (local_mode && j == 0) { if (ps > h) h = ps; }
-                        if (j - 1 >= prev_beg && j - 1 <= prev_end) {
-                            S v = (S)(cr[j - 1 - prev_beg] + ps);
+                        if (j - 1 >= q.beg && j - 1 <= q.end) {
+                            S v = (S)(cr[j - 1 - q.beg] + ps);
                             if (v > h) h = v;
                         }
-                        if (j >= prev_beg && j <= prev_end) {
-                            S v1 = (S)(cr[BMW + j - prev_beg] + ps);
-                            S v2 = (S)(cr[2 * BMW + j - prev_beg] + ps);
+                        if (j >= q.beg && j <= q.end) {
+                            S v1 = (S)(cr[BMW + j - q.beg] + ps);
+                            S v2 = (S)(cr[2 * BMW + j - q.beg] + ps);
                             if (v1 > e1v) e1v = v1;
                             if (v2 > e2v) e2v = v2;
                         }
                     }
-                    continue;
+                    return;
                 }
-                const abamd_row_meta_t pm = meta[p];
+                abamd_row_meta_t pm;
+                pm.beg = g_meta[p].beg; pm.end = g_meta[p].end; pm.off = g_meta[p].off;
                 const int64_t pbw = pm.end - pm.beg + 1;
-                const S *__restrict__ pH = arena + pm.off * 3;
-                const S *__restrict__ pE1 = pH + pbw;
-                const S *__restrict__ pE2 = pE1 + pbw;
+                const GS *__restrict__ pH = g_arena + pm.off * 3;
+                const GS *__restrict__ pE1 = pH + pbw;
+                const GS *__restrict__ pE2 = pE1 + pbw;
                 if (act) {
                     if (local_mode && j == 0) { if (ps > h) h = ps; }
                     if (j - 1 >= pm.beg && j - 1 <= pm.end) {
@@ -381,8 +508,19 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
                         if (v2 > e2v) e2v = v2;
                     }
                 }
+            };
+            /* pre_ps is all zero unless inc_path_score: skip its loads */
+            #pragma unroll
+            for (int i = 0; i < MW_NPF; ++i)
+                if (i < npre) gather(pidx[i], pf[i], ips ? (S)g_pre_ps[pk0 + i] : (S)0);
+            for (int k = pk0 + MW_NPF; k < pk1; ++k) {
+                const int p = g_pre_idx[k];
+                int4 t; mw_pred_t q;
+                const int s = ring_probe(p, t);
+                pred_resolve(p, s, t, q);
+                gather(p, q, ips ? (S)g_pre_ps[k] : (S)0);
             }
-            const S q = (S)((j == 0 || !act) ? 0 : mrow[query[j - 1]]);
+            const S q = (S)((j == 0 || !act) ? 0 : mrow[g_query[j - 1]]);
             S hpre = (S)(h + q);
             hpre = smax(hpre, smax(e1v, e2v));
             if (!act) hpre = inf_min;
@@ -447,6 +585,10 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             if (more && j == ss + MWT - 1) {
                 sc_carry[0] = hpre; sc_carry[1] = f1; sc_carry[2] = f2;
             }
+            /* this row's slot entry: after B2, so every gather of this row
+             * (none of which reads this slot) has passed; B3 publishes it */
+            if (!more && tid == 0)
+                ring_tbl[slot] = make_int4(cache_fits ? r : -1, beg, end, 0);
             if (!more && (jb.banded || local_mode || extend_mode)) {
                 /* last superchunk: fold the per-wave argmax publish into this
                  * barrier instead of paying a fourth barrier (and its store
@@ -470,13 +612,11 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
                 mw_a += mt1 - mt0;   /* band + prefetch + gather + hpre */
                 mw_b += mt2 - mt1;   /* B1 + scans + B2 + carries + fold + stores */
                 mw_c += mt3 - mt2;   /* carry publish + B3 */
+                kp_a += mt1 - mt0;
             }
 #endif
         }
-
-        if (cache_fits) { prev_ok = 1; prev_row = r; prev_beg = beg; prev_end = end; }
-        else prev_ok = 0;
-        buf_cur ^= 1;
+        KPROF_T(mt3e);
 
         if (jb.banded || local_mode || extend_mode) {
             /* per-wave argmax published under the loop's last barrier; every
@@ -505,18 +645,21 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             }
             push_ml = 0x7fffffff; push_mr = -0x7fffffff;
             if (!zdropped && jb.banded) {
-                for (int k = oo0; k < oo1; ++k) {
-                    int o = jb.out_idx[k];
+                /* every thread performs the same idempotent update so its
+                 * own later prefetch of row o is self-ordered */
+                auto push = [&](const int o) {
                     if (o == r + 1) {
                         if (rr + 1 > push_mr) push_mr = rr + 1;
                         if (ll + 1 < push_ml) push_ml = ll + 1;
                     } else {
-                        /* every thread performs the same idempotent update so
-                         * its own later prefetch of row o is self-ordered */
-                        if (rr + 1 > jb.max_right[o]) jb.max_right[o] = rr + 1;
-                        if (ll + 1 < jb.max_left[o]) jb.max_left[o] = ll + 1;
+                        if (rr + 1 > g_max_right[o]) g_max_right[o] = rr + 1;
+                        if (ll + 1 < g_max_left[o]) g_max_left[o] = ll + 1;
                     }
-                }
+                };
+                #pragma unroll
+                for (int i = 0; i < MW_NPF; ++i)
+                    if (i < oo1 - oo0) push(oidx[i]);
+                for (int k = oo0 + MW_NPF; k < oo1; ++k) push(g_out_idx[k]);
             }
             if (zdropped) break;
         } else {
@@ -526,6 +669,15 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
         {
             unsigned long long mt4 = __builtin_readcyclecounter();
             mw_d += mt4 - mt0; mw_rows += 1; /* mt0 re-read below start */
+            if (tid == 0) {
+                atomicAdd(&abamd_kprof_acc[16 + kp_cls], 1ull);
+                atomicAdd(&abamd_kprof_acc[19 + kp_cls], kp_a);
+                atomicAdd(&abamd_kprof_acc[22 + kp_cls], mt4 - mt3e);
+                atomicAdd(&abamd_kprof_acc[25 + kp_cls], mt4 - mt0);
+                if (!cache_fits) atomicAdd(&abamd_kprof_acc[28], 1ull);
+                if (npre > MW_NPF) atomicAdd(&abamd_kprof_acc[29], 1ull);
+                atomicAdd(&abamd_kprof_acc[30], (unsigned long long)npre);
+            }
         }
 #endif
     }
@@ -575,7 +727,8 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
      * per-wave local-scan + cross-wave-carry machinery of the forward pass
      * (same associativity/headroom argument). */
     __shared__ int bt_go, bt_bi_s, bt_bj_s;
-    __shared__ S fbuf[2 * BMW];
+    /* the F window aliases the row ring, dead since the barrier above */
+    S *fbuf = &ring_lds[0][0];
     /* walk state: only thread 0's copies advance */
     int bi = best_i, bj = best_j, start_i = best_i, start_j = best_j;
     int cur_op = 0x1f, n_c = 0, status = ABAMD_JOB_OK;
@@ -804,6 +957,15 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             }
         }
     }
+}
+
+extern "C" int abamd_dp_ring_depth(void) {
+    /* read per call (one getenv per job build): tests flip it in-process */
+    const char *e = getenv("ABPOA_AMD_DP_RING");
+    int d = (e && *e) ? atoi(e) : ABAMD_DP_RING_MAX;
+    if (d < 1) d = 1;
+    if (d > ABAMD_DP_RING_MAX) d = ABAMD_DP_RING_MAX;
+    return d;
 }
 
 extern "C" void abamd_launch_cg_i16(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
