@@ -1,34 +1,42 @@
 /* CDNA4 (gfx950) aligner core: adaptive-banded sequence-to-graph DP.
  *
- * One wavefront (64 lanes) per alignment job, 4 jobs per 256-thread
- * workgroup. The wave sweeps the graph's topologically-sorted rows; within a
- * row the band is processed in 64-cell register chunks:
- *   - M/E gather from predecessor rows. The immediately preceding row's H/E
- *     planes are kept in a double-buffered LDS cache (BMAX cells) — a
+ * One alignment job per 512-thread workgroup (8 wavefronts). The block
+ * sweeps the graph's topologically-sorted rows; the 8 waves cover a row's
+ * band at once, in 512-cell superchunks where the band is wider:
+ *   - M/E gather from predecessor rows. Recent rows are kept in LDS — a
  *     ~50-cycle LDS read replaces a ~900-cycle HBM round-trip on the
- *     row-to-row dependent chain. Other predecessors (and bands wider than
- *     the cache) read the banded HBM arena with coalesced 2/4-byte loads.
- *     (r-1 is the only predecessor for the first reads of a set only; the
- *     convex multi-wave kernel below keeps a ring of recent rows instead.)
- *   - the F (insertion) recurrence is a wavefront max-plus log-scan
- *     (__shfl_up, 6 doubling steps) with a sequential carry between chunks,
+ *     row-to-row dependent chain: the convex kernel keeps a ring of the last
+ *     rows, the affine and linear kernels a double-buffered copy of the
+ *     previous row. Other predecessors (and bands wider than BMW cells)
+ *     read the banded HBM arena with coalesced 2/4-byte loads;
+ *   - the F (insertion) recurrence is a per-wave max-plus scan (DPP row
+ *     shifts + readlane carries) plus a cross-wave carry recurrence over
+ *     the published wave edges, with a carry between superchunks;
  *   - the banded planes stream to the HBM arena with coalesced stores
  *     (convex: H,E1,E2 only — the F planes are recomputed from stored H at
- *     backtrack time; affine: H,E1,F1; linear: H),
- *   - the row argmax (adaptive band steering) is a wavefront reduction,
- *   - per-row band metadata is one 16-byte abamd_row_meta_t load.
+ *     backtrack time; affine: H,E1,F1; linear: H);
+ *   - the row argmax (adaptive band steering) is a per-wave reduction and
+ *     an 8-way combine from LDS;
+ *   - per-row band metadata is one 16-byte abamd_row_meta_t;
+ *   - thread 0 backtracks in the kernel.
  * Integer max-plus throughout: MFMA does not apply; the target bound is the
  * 6 B/cell (convex int16) HBM plane traffic.
+ *
+ * Three kernels, each instantiated for int16 and for the int32 overflow
+ * rescore, each serving global, local and extension mode: cg_global_mw_kernel
+ * (convex gaps, the north-star path), ag_global_mw_kernel (affine) and
+ * lg_global_mw_kernel (linear). The last two are the "multi-wave frame"
+ * section plus their recurrence. The convex kernel keeps its own text (rolled
+ * predecessors, row ring, global-address-space pointers): calling the frame
+ * for the three blocks it has in common measured 0.5 % lower at the bench
+ * (DESIGN.md §6b); small source changes move these kernels' SGPR spills.
  *
  * Numerics are bit-identical to oracle/ref_core.c (and the reference x86
  * build): int16 arithmetic wraps (non-saturating _mm*_add_epi16 semantics),
  * reproduced by truncating to the score type after every add/sub. Recurrence
  * and backtrack follow abpoa_align_simd.c:935-1074 / :309-458; band formulas
- * abpoa_align.h:34-35.
- *
- * This file covers global alignment with convex gaps (the north-star path),
- * int16 with int32 overflow rescore. Affine/linear gap and local/extension
- * variants are host-dispatched and tracked in DESIGN.md §7.
+ * abpoa_align.h:34-35. The host picks the kernel by gap model and score
+ * width (gpu_align.cpp, gpu_batch_resident.cpp).
  */
 #include <hip/hip_runtime.h>
 #include "gpu_core.h"
@@ -59,14 +67,13 @@ extern "C" void abamd_kprof_reset(void) {
 #endif
 
 #define WAVE 64
-#define JOBS_PER_BLOCK 4
-/* LDS previous-row cache width (cells). Default bands are ~230-450 cells
- * (w = wb + wf*qlen = 110 at the north-star shape); wider rows fall back to
- * arena reads. */
-#define ABAMD_BMAX 512
-/* int32 rounds halve the cache width to keep LDS within 4 resident blocks/CU */
-template <typename S> struct BmaxOf { static constexpr int v = ABAMD_BMAX; };
-template <> struct BmaxOf<int32_t> { static constexpr int v = 384; };
+#define MWAVES 8
+#define MWT (WAVE * MWAVES)
+/* LDS row-cache width (cells): a ring slot of the convex kernel, the
+ * previous-row buffer of the affine and linear ones. Default bands are
+ * ~230-450 cells (w = wb + wf*qlen = 110 at the north-star shape); wider
+ * rows are re-read from the arena. */
+#define BMW 512
 
 template <typename S>
 __device__ __forceinline__ S smax(S a, S b) { return a > b ? a : b; }
@@ -149,18 +156,294 @@ __device__ static int dev_push_cigar(uint64_t *cig, int *n_c, int cap, int op, i
 }
 
 /* ------------------------------------------------------------------ */
+/* The multi-wave frame: ONE JOB PER 512-THREAD BLOCK, and what the     */
+/* affine and linear kernels do around their recurrences, once. Every   */
+/* thread of the block calls a helper with the same arguments unless    */
+/* the helper says otherwise. No helper holds a barrier (the kernels    */
+/* place them, and say what each one orders) and none knows which gap   */
+/* model called it.                                                     */
+/* ------------------------------------------------------------------ */
+
+/* adaptive band state init (abpoa_topological_sort:347-353 + first_dp);
+ * the caller's next barrier publishes it */
+__device__ __forceinline__ void mw_steer_init(const abamd_gpu_job_t &jb, int tid) {
+    for (int i = tid; i < jb.n_rows; i += MWT) {
+        jb.max_left[i] = jb.node_n_init;
+        jb.max_right[i] = 0;
+    }
+    if (tid == 0) { jb.max_left[0] = 0; jb.max_right[0] = 0; }
+    for (int k = jb.out_off[0] + tid; k < jb.out_off[1]; k += MWT) {
+        int o = jb.out_idx[k];
+        jb.max_left[o] = 1; jb.max_right[o] = 1;
+    }
+}
+
+/* band end of row 0 (GET_AD_DP_END, abpoa_align.h:35) */
+__device__ __forceinline__ int mw_first_row_end(const abamd_gpu_job_t &jb, int end_remain) {
+    if (!jb.banded) return jb.qlen;
+    const int mr = jb.max_remain[0] - end_remain - 1;
+    const int t = jb.max_right[0] > jb.qlen - mr ? jb.max_right[0] : jb.qlen - mr;
+    return (jb.qlen < t + jb.w) ? jb.qlen : t + jb.w;
+}
+
+/* A row's scalars. The kernels load them one row ahead, so that the latency
+ * hides under the previous row: `mw_row_t nxt` holds row r+1 while row r is
+ * computed. A steering push r -> r+1 therefore never goes through memory:
+ * max_left/max_right of row r+1 were loaded before row r could push, so the
+ * push is merged into nxt (the same copy in every thread). */
+struct mw_row_t {
+    int pk0, pk1;       /* its predecessors: pre_idx[pk0 .. pk1) */
+    int oo0, oo1;       /* its out-edges: out_idx[oo0 .. oo1) */
+    int remain;         /* max_remain */
+    int ml, mr;         /* max_left / max_right */
+    int pidx0, ps0;     /* first predecessor and its path score */
+
+    __device__ __forceinline__ void load(const abamd_gpu_job_t &jb, int r, int r_next) {
+        pk1 = jb.pre_off[r_next];
+        oo1 = jb.out_off[r_next];
+        remain = jb.max_remain[r];
+        ml = jb.max_left[r];
+        mr = jb.max_right[r];
+        pidx0 = jb.pre_idx[pk0];
+        ps0 = jb.pre_ps[pk0];
+    }
+    __device__ __forceinline__ void first(const abamd_gpu_job_t &jb) { /* row 1 */
+        pk0 = jb.pre_off[1];
+        oo0 = jb.out_off[1];
+        load(jb, 1, 2 <= jb.n_rows ? 2 : jb.n_rows);
+    }
+    __device__ __forceinline__ void advance(const abamd_gpu_job_t &jb, int r) { /* to row r */
+        pk0 = pk1;
+        oo0 = oo1;
+        load(jb, r, r + 1);
+    }
+};
+
+/* the row whose band the LDS previous-row cache holds, if any */
+struct mw_prev_t { int ok, row, beg, end; };
+
+/* adaptive band of a row (GET_AD_DP_BEGIN/END, abpoa_align.h:34-35): the
+ * steering maxima of the row, widened by w, and never starting left of the
+ * leftmost band start among its predecessors */
+__device__ __forceinline__ void mw_row_band(const abamd_gpu_job_t &jb, const abamd_row_meta_t *meta,
+                                            const mw_row_t &row, const mw_prev_t &prev,
+                                            int end_remain, int &beg, int &end) {
+    if (!jb.banded) { beg = 0; end = jb.qlen; return; }
+    const int mr = row.remain - end_remain - 1;
+    int lo = row.ml < jb.qlen - mr ? row.ml : jb.qlen - mr;
+    beg = lo - jb.w; if (beg < 0) beg = 0;
+    int hi = row.mr > jb.qlen - mr ? row.mr : jb.qlen - mr;
+    end = hi + jb.w; if (end > jb.qlen) end = jb.qlen;
+    int min_pre_beg;
+    if (row.pk1 - row.pk0 == 1) {
+        min_pre_beg = (prev.ok && row.pidx0 == prev.row) ? prev.beg : meta[row.pidx0].beg;
+    } else {
+        min_pre_beg = 0x7fffffff;
+        for (int k = row.pk0; k < row.pk1; ++k) {
+            const int pidx = jb.pre_idx[k];
+            int pb = (prev.ok && pidx == prev.row) ? prev.beg : meta[pidx].beg;
+            if (pb < min_pre_beg) min_pre_beg = pb;
+        }
+    }
+    if (beg < min_pre_beg) beg = min_pre_beg;
+}
+
+/* Row argmax (simd_abpoa_max_in_row: leftmost and rightmost column of the
+ * maximum). Each thread brings the maximum over its own cells; lane 0 of
+ * every wave publishes the wave's into sc_red[3 * MWAVES]. The kernels call
+ * this in a row's last superchunk, so the barrier that ends the superchunk
+ * publishes it as well. */
+struct mw_rowmax_t { int mv, ll, rr; };
+
+/* the argmax steers the band and is the score of local and extension mode;
+ * an unbanded global job needs none */
+__device__ __forceinline__ bool mw_needs_rowmax(const abamd_gpu_job_t &jb) {
+    return jb.banded || jb.align_mode == 1 || jb.align_mode == 2;
+}
+
+template <typename S>
+__device__ __forceinline__ void mw_rowmax_publish(int *sc_red, int wv, int lane,
+                                                  S lmax, int lleft, int lright) {
+    int mvw = wave_red_max_i32((int)lmax);
+    int llw = ((int)lmax == mvw && lleft >= 0) ? lleft : 0x7fffffff;
+    int rrw = ((int)lmax == mvw && lright >= 0) ? lright : -1;
+    llw = wave_red_min_i32(llw);
+    rrw = wave_red_max_i32(rrw);
+    if (lane == 0) {
+        sc_red[wv] = mvw;
+        sc_red[MWAVES + wv] = llw;
+        sc_red[2 * MWAVES + wv] = rrw;
+    }
+}
+
+/* every thread repeats the 8-way combine from LDS (uniform result) */
+__device__ __forceinline__ mw_rowmax_t mw_rowmax_combine(const int *sc_red) {
+    mw_rowmax_t m = { sc_red[0], sc_red[MWAVES], sc_red[2 * MWAVES] };
+    #pragma unroll
+    for (int ww = 1; ww < MWAVES; ++ww) {
+        int m2 = sc_red[ww];
+        if (m2 > m.mv) { m.mv = m2; m.ll = sc_red[MWAVES + ww]; m.rr = sc_red[2 * MWAVES + ww]; }
+        else if (m2 == m.mv) {
+            if (sc_red[MWAVES + ww] < m.ll) m.ll = sc_red[MWAVES + ww];
+            if (sc_red[2 * MWAVES + ww] > m.rr) m.rr = sc_red[2 * MWAVES + ww];
+        }
+    }
+    return m;
+}
+
+/* running best cell of local and extension mode (starts as { inf_min, 0, 0,
+ * max_remain[0], 0 }); zdropped ends the row loop */
+struct mw_best_t { int32_t score; int i, j, remain, zdropped; };
+
+__device__ __forceinline__ void mw_best_update(const abamd_gpu_job_t &jb, mw_best_t &b,
+                                               int r, int row_remain, const mw_rowmax_t &m) {
+    if (jb.align_mode == 1) {
+        if (m.mv > b.score) { b.score = m.mv; b.i = r; b.j = m.ll; }
+    } else if (jb.align_mode == 2) {
+        if (m.mv > b.score) {
+            b.score = m.mv; b.i = r; b.j = m.rr;
+            b.remain = row_remain;
+        } else if (jb.zdrop > 0) {
+            int delta = b.remain - row_remain;
+            int dd = delta - (m.rr - b.j); if (dd < 0) dd = -dd;
+            if (b.score - m.mv > jb.zdrop + jb.e1 * dd) b.zdropped = 1;
+        }
+    }
+}
+
+/* band steering: row r pushes its argmax columns to its out-edges; nxt
+ * holds row r+1. Every thread performs the same idempotent update, so its
+ * own later load of max_left/max_right of row o is self-ordered. */
+__device__ __forceinline__ void mw_steer_push(const abamd_gpu_job_t &jb, const mw_row_t &row, int r,
+                                              const mw_rowmax_t &m, mw_row_t &nxt) {
+    for (int k = row.oo0; k < row.oo1; ++k) {
+        int o = jb.out_idx[k];
+        if (o == r + 1) {
+            if (m.rr + 1 > nxt.mr) nxt.mr = m.rr + 1;
+            if (m.ll + 1 < nxt.ml) nxt.ml = m.ll + 1;
+        } else {
+            if (m.rr + 1 > jb.max_right[o]) jb.max_right[o] = m.rr + 1;
+            if (m.ll + 1 < jb.max_left[o]) jb.max_left[o] = m.ll + 1;
+        }
+    }
+}
+
+/* What follows the last barrier of row r: combine the published argmax, keep
+ * the running best, push the steering to the out-edges. Returns nonzero
+ * when the z-drop ends the row loop. */
+__device__ __forceinline__ int mw_row_close(const abamd_gpu_job_t &jb, const int *sc_red,
+                                            const mw_row_t &row, int r, mw_best_t &run,
+                                            mw_row_t &nxt) {
+    if (!mw_needs_rowmax(jb)) return 0;
+    const mw_rowmax_t rm = mw_rowmax_combine(sc_red);
+    mw_best_update(jb, run, r, row.remain, rm);
+    if (run.zdropped) return 1;
+    if (jb.banded) mw_steer_push(jb, row, r, rm, nxt);
+    return 0;
+}
+
+/* Reserve row r's band [beg, end] in the arena (`used` counts cells per
+ * plane) and record it in row_meta. Returns the row's offset, or -1 when the
+ * arena is full. */
+__device__ __forceinline__ int64_t mw_row_reserve(const abamd_gpu_job_t &jb, abamd_row_meta_t *meta,
+                                                  int tid, int r, int beg, int end, int64_t &used) {
+    const int64_t bw = end - beg + 1;
+    if (used + bw > jb.arena_cap) return -1;
+    const int64_t off = used;
+    if (tid == 0) { meta[r].beg = beg; meta[r].end = end; meta[r].off = off; }
+    used += bw;
+    return off;
+}
+
+/* Where the backtrack starts: the running best, or in global mode the best
+ * H at the band end of the sink's predecessors. `planes` is the number of
+ * planes a row takes in the arena. */
+template <typename S>
+__device__ __forceinline__ void mw_final_best(const abamd_gpu_job_t &jb, const mw_best_t &run, int planes,
+                                              int32_t &best_score, int &best_i, int &best_j) {
+    best_score = run.score; best_i = run.i; best_j = run.j;
+    if (jb.align_mode != 0) return;
+    const abamd_row_meta_t *meta = (const abamd_row_meta_t*)jb.row_meta;
+    best_score = jb.inf_min; best_i = 0; best_j = 0;
+    for (int k = jb.pre_off[jb.n_rows - 1]; k < jb.pre_off[jb.n_rows]; ++k) {
+        const int p = jb.pre_idx[k];
+        const abamd_row_meta_t pm = meta[p];
+        int e = pm.end < jb.qlen ? pm.end : jb.qlen;
+        const S *pH = (const S*)jb.arena + pm.off * planes;
+        int32_t sc = (e >= pm.beg) ? (int32_t)pH[e - pm.beg] : jb.inf_min;
+        if (sc > best_score) { best_score = sc; best_i = p; best_j = e; }
+    }
+}
+
+/* The backtrack walk of one thread, from cell (best_i, best_j) towards the
+ * source: position, CIGAR under construction and the counters the result
+ * reports. */
+struct mw_walk_t {
+    int bi, bj, id;         /* row, column, node id of the row */
+    int start_i, start_j;   /* last cell visited */
+    int look_end, put_right;
+    int n_c, status, n_aln, n_matched;
+};
+
+__device__ __forceinline__ mw_walk_t mw_walk_begin(const abamd_gpu_job_t &jb, int best_i, int best_j) {
+    mw_walk_t wk = { best_i, best_j, jb.row_node_id[best_i], best_i, best_j,
+                     jb.put_gap_at_end, jb.put_gap_on_right, 0, ABAMD_JOB_OK, 0, 0 };
+    if (best_j < jb.qlen)
+        dev_push_cigar(jb.cigar, &wk.n_c, jb.cigar_cap, 1, jb.qlen - best_j, -1, jb.qlen - 1, &wk.status);
+    return wk;
+}
+
+/* match step: the first predecessor p (of pre_idx[pq0 .. pq1), the row's)
+ * with H[p][bj-1] + s + path score == Hj takes the walk to (p, bj-1).
+ * Returns whether there was one. */
+template <typename S>
+__device__ __forceinline__ int mw_walk_match(const abamd_gpu_job_t &jb, mw_walk_t &wk, int planes,
+                                             int pq0, int pq1, S s, int is_match, S Hj) {
+    const abamd_row_meta_t *meta = (const abamd_row_meta_t*)jb.row_meta;
+    for (int k = pq0; k < pq1; ++k) {
+        const int p = jb.pre_idx[k];
+        const S ps = (S)jb.pre_ps[k];
+        const abamd_row_meta_t pm = meta[p];
+        if (wk.bj - 1 < pm.beg || wk.bj - 1 > pm.end) continue;
+        const S *pH = (const S*)jb.arena + pm.off * planes;
+        if ((S)(pH[wk.bj - 1 - pm.beg] + s + ps) == Hj) {
+            dev_push_cigar(jb.cigar, &wk.n_c, jb.cigar_cap, 0, 1, wk.id, wk.bj - 1, &wk.status);
+            wk.bi = p; --wk.bj; wk.id = jb.row_node_id[wk.bi];
+            ++wk.n_aln; wk.n_matched += is_match;
+            return 1;
+        }
+    }
+    return 0;
+}
+
+/* close the CIGAR (leading insertion when the walk stopped at column bj > 0)
+ * and write the job's result */
+__device__ __forceinline__ void mw_walk_end(const abamd_gpu_job_t &jb, abamd_gpu_res_t *res,
+                                            mw_walk_t &wk, int best_i, int best_j) {
+    if (wk.status == ABAMD_JOB_OK && wk.bj > 0)
+        dev_push_cigar(jb.cigar, &wk.n_c, jb.cigar_cap, 1, wk.bj, -1, wk.bj - 1, &wk.status);
+    res->status = wk.status;
+    res->n_cigar = wk.n_c;
+    res->n_aln_bases = wk.n_aln;
+    res->n_matched_bases = wk.n_matched;
+    res->node_e = jb.row_node_id[best_i]; res->query_e = best_j - 1;
+    res->node_s = jb.row_node_id[wk.start_i]; res->query_s = wk.start_j - 1;
+}
+
+/* ------------------------------------------------------------------ */
 /* Multi-wave convex kernel: ONE JOB PER 512-THREAD BLOCK.              */
 /*                                                                      */
-/* The one-wave kernel above is instruction-ISSUE bound: a lone wave    */
-/* on a SIMD issues one VALU op per 4 cycles, and a ~350-instruction    */
-/* chunk body makes a typical 340-cell row cost ~21k cycles (kprof).    */
+/* Round 1 ran one wavefront per job and was instruction-ISSUE bound: a */
+/* lone wave on a SIMD issues one VALU op per 4 cycles, and a ~350-     */
+/* instruction chunk body made a typical 340-cell row cost ~21k cycles. */
 /* Here 8 waves cover the whole band at once: the M/E gather, H fold,   */
 /* stores and argmax are embarrassingly lane-parallel, and the F        */
 /* (insertion) max-plus chain splits into per-wave local scans plus a   */
 /* cross-wave carry recurrence over the 8 published wave edges — the    */
 /* regrouped decays are bit-identical because wrapping addition is      */
-/* associative and the inf_min headroom (+512*ext_max, the same bound   */
-/* the one-wave scan relies on) keeps every comparison un-wrapped.      */
+/* associative and the inf_min headroom (+512*ext_max, the same margin  */
+/* the reference's vector code relies on) keeps every comparison        */
+/* un-wrapped.                                                          */
 /* Three block barriers per row replace ~5 serial chunk iterations.     */
 /*                                                                      */
 /* Row ring. Only the first few reads see a chain-like graph: after     */
@@ -184,9 +467,6 @@ __device__ static int dev_push_cigar(uint64_t *cig, int *n_c, int cap, int op, i
 /* or row_meta lookups are done once per row and shared by the band     */
 /* start (min_pre_beg) and the gather.                                  */
 /* ------------------------------------------------------------------ */
-#define MWAVES 8
-#define MWT (WAVE * MWAVES)
-#define BMW 512 /* ring slot width (cells); wider bands re-read the arena */
 /* ring slots: rows r-1 .. r-ABAMD_DP_RING_MAX are readable while row r is
  * written. int32: 11 x 3 x 512 x 4 B = 66 KiB (+3 KiB matrix), under the
  * 80 KiB that keeps two blocks per CU; int16 takes half. Depth 10 is where
@@ -980,685 +1260,13 @@ extern "C" void abamd_launch_cg_i32(const abamd_gpu_job_t *dev_jobs, abamd_gpu_r
 }
 
 /* ------------------------------------------------------------------ */
-/* Affine-gap global kernel: 3 planes (H,E1,F1).                       */
-/* Reference core simd_abpoa_ag_dp (abpoa_align_simd.c:817-933):       */
-/* the F chain feeds from H BEFORE the E fold, and the stored E is     */
-/* inf_min when the insertion won the cell (SIMDSetIfEqual, :930).     */
-/* Backtrack: simd_abpoa_ag_backtrack (:196-307).                      */
-/* ------------------------------------------------------------------ */
-template <typename S>
-__global__ __launch_bounds__(WAVE * JOBS_PER_BLOCK, 7)
-void ag_global_kernel(const abamd_gpu_job_t *__restrict__ jobs,
-                      abamd_gpu_res_t *__restrict__ results, int n_jobs) {
-    const int wid = threadIdx.x / WAVE;
-    const int jid = blockIdx.x * JOBS_PER_BLOCK + wid;
-    const int lane = threadIdx.x % WAVE;
-
-    __shared__ int mat_lds[27 * 27];
-    constexpr int BMAX = BmaxOf<S>::v;
-    /* cache H and E1 of the previous row */
-    __shared__ S prev_lds[JOBS_PER_BLOCK][2][2 * BMAX];
-    {
-        const int m0 = jobs[0].m;
-        const int *mat0 = jobs[0].mat;
-        for (int i = threadIdx.x; i < m0 * m0; i += WAVE * JOBS_PER_BLOCK)
-            mat_lds[i] = mat0[i];
-    }
-    __syncthreads();
-    if (jid >= n_jobs) return;
-    /* by VALUE: every field lives in registers (uniform loads become
-       s_loads into SGPRs) — a reference would re-load fields from global
-       memory inside the row loop because arena/steering stores could alias
-       the jobs array in the compiler's view */
-    const abamd_gpu_job_t jb = jobs[jid];
-    abamd_gpu_res_t *res = &results[jid];
-    abamd_row_meta_t *__restrict__ meta = (abamd_row_meta_t*)jb.row_meta;
-
-    const int qlen = jb.qlen, n_rows = jb.n_rows, w = jb.w, m = jb.m;
-    const S inf_min = (S)jb.inf_min;
-    const S e1 = (S)jb.e1, oe1 = (S)jb.oe1;
-    const int local_mode = jb.align_mode == 1, extend_mode = jb.align_mode == 2;
-    int32_t run_best = jb.inf_min;
-    int run_best_i = 0, run_best_j = 0, run_best_remain = jb.max_remain[0];
-    int zdropped = 0;
-    const int end_remain = jb.max_remain[n_rows - 1];
-    S *arena = (S*)jb.arena;
-    const uint8_t *__restrict__ query = jb.query;
-
-    if (lane == 0) { res->status = ABAMD_JOB_OK; res->n_cigar = 0; }
-
-    for (int i = lane; i < n_rows; i += WAVE) {
-        jb.max_left[i] = jb.node_n_init;
-        jb.max_right[i] = 0;
-    }
-    if (lane == 0) { jb.max_left[0] = 0; jb.max_right[0] = 0; }
-    for (int k = jb.out_off[0] + lane; k < jb.out_off[1]; k += WAVE) {
-        int o = jb.out_idx[k];
-        jb.max_left[o] = 1; jb.max_right[o] = 1;
-    }
-
-    int buf_cur = 0;
-    int prev_ok = 0, prev_row = -1, prev_beg = 0, prev_end = -1;
-
-    /* first row (simd_abpoa_ag_first_dp, abpoa_align_simd.c:651-667) */
-    int64_t used;
-    {
-        int mr = jb.max_remain[0] - end_remain - 1;
-        int end0;
-        if (jb.banded) {
-            int t = jb.max_right[0] > qlen - mr ? jb.max_right[0] : qlen - mr;
-            end0 = (qlen < t + w) ? qlen : t + w;
-        } else end0 = qlen;
-        if (lane == 0) { meta[0].beg = 0; meta[0].end = end0; meta[0].off = 0; }
-        int64_t bw = end0 + 1;
-        used = bw;
-        S *H = arena, *E1 = arena + bw, *F1 = arena + 2 * bw;
-        S *c = &prev_lds[wid][buf_cur][0];
-        const int fits = end0 + 1 <= BMAX;
-        for (int j = lane; j <= end0; j += WAVE) {
-            S hv, e1v2;
-            if (local_mode) {
-                hv = 0; e1v2 = 0; F1[j] = 0;
-            } else if (j == 0) {
-                hv = 0; e1v2 = (S)(0 - oe1);
-                F1[0] = inf_min;
-            } else {
-                S f1 = (S)(-(jb.o1 + jb.e1 * j));
-                F1[j] = f1;
-                hv = f1; e1v2 = inf_min;
-            }
-            H[j] = hv; E1[j] = e1v2;
-            if (fits) { c[j] = hv; c[BMAX + j] = e1v2; }
-        }
-        if (fits) { prev_ok = 1; prev_row = 0; prev_beg = 0; prev_end = end0; }
-        buf_cur ^= 1;
-    }
-
-    for (int r = 1; r < n_rows - 1; ++r) {
-        const int pk0 = jb.pre_off[r], pk1 = jb.pre_off[r + 1];
-        int beg, end;
-        {
-            int mr = jb.max_remain[r] - end_remain - 1;
-            if (jb.banded) {
-                int ml = jb.max_left[r], mrr = jb.max_right[r];
-                int lo = ml < qlen - mr ? ml : qlen - mr;
-                beg = lo - w; if (beg < 0) beg = 0;
-                int hi = mrr > qlen - mr ? mrr : qlen - mr;
-                end = hi + w; if (end > qlen) end = qlen;
-                int min_pre_beg = 0x7fffffff;
-                for (int k = pk0; k < pk1; ++k) {
-                    const int pidx = jb.pre_idx[k];
-                    int pb = (prev_ok && pidx == prev_row) ? prev_beg : meta[pidx].beg;
-                    if (pb < min_pre_beg) min_pre_beg = pb;
-                }
-                if (beg < min_pre_beg) beg = min_pre_beg;
-            } else { beg = 0; end = qlen; }
-        }
-        const int64_t bw = end - beg + 1;
-        if (used + bw > jb.arena_cap) { if (lane == 0) res->status = ABAMD_JOB_ARENA_OVERFLOW; return; }
-        const int64_t off = used;
-        if (lane == 0) { meta[r].beg = beg; meta[r].end = end; meta[r].off = off; }
-        used += bw;
-        S *H = arena + off * 3, *E1r = H + bw, *F1r = E1r + bw;
-        const uint8_t base = jb.row_base[r];
-        const int *mrow = &mat_lds[base * m];
-        const int cache_fits = bw <= BMAX;
-        S *cw = &prev_lds[wid][buf_cur][0];
-        const S *cr = &prev_lds[wid][buf_cur ^ 1][0];
-
-        S carry_hm = inf_min, f1c = inf_min;
-        S lmax = inf_min; int lleft = -1, lright = -1;
-
-        for (int cs = beg; cs <= end; cs += WAVE) {
-            const int j = cs + lane;
-            const bool act = j <= end;
-            S h = inf_min, e1v = inf_min;
-            for (int k = pk0; k < pk1; ++k) {
-                const int p = jb.pre_idx[k];
-                const S ps = (S)jb.pre_ps[k];
-                if (prev_ok && p == prev_row) {
-                    if (act) {
-                        if (local_mode && j == 0) { if (ps > h) h = ps; }
-                        if (j - 1 >= prev_beg && j - 1 <= prev_end) {
-                            S v = (S)(cr[j - 1 - prev_beg] + ps);
-                            if (v > h) h = v;
-                        }
-                        if (j >= prev_beg && j <= prev_end) {
-                            S v1 = (S)(cr[BMAX + j - prev_beg] + ps);
-                            if (v1 > e1v) e1v = v1;
-                        }
-                    }
-                    continue;
-                }
-                const abamd_row_meta_t pm = meta[p];
-                const int64_t pbw = pm.end - pm.beg + 1;
-                const S *__restrict__ pH = arena + pm.off * 3;
-                const S *__restrict__ pE1 = pH + pbw;
-                if (act) {
-                    if (local_mode && j == 0) { if (ps > h) h = ps; }
-                    if (j - 1 >= pm.beg && j - 1 <= pm.end) {
-                        S v = (S)(pH[j - 1 - pm.beg] + ps);
-                        if (v > h) h = v;
-                    }
-                    if (j >= pm.beg && j <= pm.end) {
-                        S v1 = (S)(pE1[j - pm.beg] + ps);
-                        if (v1 > e1v) e1v = v1;
-                    }
-                }
-            }
-            const S q = (S)((j == 0 || !act) ? 0 : mrow[query[j - 1]]);
-            S hm = (S)(h + q);   /* M+q: the F chain feeds from this, pre-E */
-            if (!act) hm = inf_min;
-
-            S hmshift = (S)__shfl_up((int)hm, 1);
-            S c1;
-            if (lane == 0) {
-                if (cs == beg) c1 = (S)(inf_min - oe1);
-                else c1 = smax((S)(carry_hm - oe1), (S)(f1c - e1));
-            } else c1 = (S)(hmshift - oe1);
-            S f1 = scan_maxplus(c1, jb.e1, inf_min, lane);
-            carry_hm = (S)__builtin_amdgcn_readlane((int)hm, WAVE - 1);
-            f1c = (S)__builtin_amdgcn_readlane((int)f1, WAVE - 1);
-
-            S tmp = smax(hm, e1v);
-            S hf = smax(tmp, f1);
-            if (local_mode) hf = smax(hf, (S)0);
-            S e1n = (hf == tmp) ? smax((S)(e1v - e1), (S)(hf - oe1))
-                                : (local_mode ? (S)0 : inf_min);
-            if (act) {
-                H[j - beg] = hf; E1r[j - beg] = e1n; F1r[j - beg] = f1;
-                if (cache_fits) { cw[j - beg] = hf; cw[BMAX + j - beg] = e1n; }
-                if (hf > lmax) { lmax = hf; lleft = j; lright = j; }
-                else if (hf == lmax) { lright = j; }
-            }
-        }
-
-        if (cache_fits) { prev_ok = 1; prev_row = r; prev_beg = beg; prev_end = end; }
-        else prev_ok = 0;
-        buf_cur ^= 1;
-
-        if (jb.banded || local_mode || extend_mode) {
-            int mv = wave_red_max_i32((int)lmax);
-            int ll = ((int)lmax == mv && lleft >= 0) ? lleft : 0x7fffffff;
-            int rr = ((int)lmax == mv && lright >= 0) ? lright : -1;
-            ll = wave_red_min_i32(ll);
-            rr = wave_red_max_i32(rr);
-            if (local_mode) {
-                if (mv > run_best) { run_best = mv; run_best_i = r; run_best_j = ll; }
-            } else if (extend_mode) {
-                if (mv > run_best) {
-                    run_best = mv; run_best_i = r; run_best_j = rr;
-                    run_best_remain = jb.max_remain[r];
-                } else if (jb.zdrop > 0) {
-                    int delta = run_best_remain - jb.max_remain[r];
-                    int dd = delta - (rr - run_best_j); if (dd < 0) dd = -dd;
-                    if (run_best - mv > jb.zdrop + jb.e1 * dd) zdropped = 1;
-                }
-            }
-            if (!zdropped && jb.banded) {
-                for (int k = jb.out_off[r] + lane; k < jb.out_off[r + 1]; k += WAVE) {
-                    int o = jb.out_idx[k];
-                    if (rr + 1 > jb.max_right[o]) jb.max_right[o] = rr + 1;
-                    if (ll + 1 < jb.max_left[o]) jb.max_left[o] = ll + 1;
-                }
-            }
-            if (zdropped) break;
-        }
-    }
-
-    if (lane == 0) res->cells = used;
-    if (lane != 0) return;
-
-    int32_t best_score = run_best;
-    int best_i = run_best_i, best_j = run_best_j;
-    if (jb.align_mode == 0) {
-        best_score = jb.inf_min; best_i = 0; best_j = 0;
-        for (int k = jb.pre_off[n_rows - 1]; k < jb.pre_off[n_rows]; ++k) {
-            const int p = jb.pre_idx[k];
-            const abamd_row_meta_t pm = meta[p];
-            int e = pm.end < qlen ? pm.end : qlen;
-            const S *pH = arena + pm.off * 3;
-            int32_t sc = (e >= pm.beg) ? (int32_t)pH[e - pm.beg] : jb.inf_min;
-            if (sc > best_score) { best_score = sc; best_i = p; best_j = e; }
-        }
-    }
-    res->best_score = best_score;
-    res->best_i = best_i; res->best_j = best_j;
-    if (!jb.ret_cigar) return;
-
-    { /* simd_abpoa_ag_backtrack (:196-307) */
-        int bi = best_i, bj = best_j, start_i = best_i, start_j = best_j;
-        int cur_op = 0x1f, n_c = 0, status = ABAMD_JOB_OK;
-        int look_end = jb.put_gap_at_end, put_right = jb.put_gap_on_right;
-        int n_aln = 0, n_matched = 0;
-        uint64_t *cig = jb.cigar;
-        int id = jb.row_node_id[bi];
-        if (best_j < qlen) dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, qlen - best_j, -1, qlen - 1, &status);
-        while (bi > 0 && bj > 0 && status == ABAMD_JOB_OK) {
-            const abamd_row_meta_t bm = meta[bi];
-            const int rb = bm.beg, re = bm.end;
-            const int64_t bw = re - rb + 1;
-            const S *H = arena + bm.off * 3;
-            const S *E1r = H + bw, *F1r = E1r + bw;
-            const S Hj = (bj >= rb && bj <= re) ? H[bj - rb] : inf_min;
-            const S Hjm1 = (bj - 1 >= rb && bj - 1 <= re) ? H[bj - 1 - rb] : inf_min;
-            const S E1j = (bj >= rb && bj <= re) ? E1r[bj - rb] : inf_min;
-            const S F1j = (bj >= rb && bj <= re) ? F1r[bj - rb] : inf_min;
-            const S F1jm1 = (bj - 1 >= rb && bj - 1 <= re) ? F1r[bj - 1 - rb] : inf_min;
-            if (local_mode && Hj == 0) break;
-            start_i = bi; start_j = bj;
-            const int pq0 = jb.pre_off[bi], pq1 = jb.pre_off[bi + 1];
-            const S s = (S)mat_lds[m * jb.row_base[bi] + query[bj - 1]];
-            const int is_match = jb.row_base[bi] == query[bj - 1];
-            int hit = 0;
-            if (put_right == 0 && look_end == 0 && (cur_op & 0x1)) {
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj - 1 < pm.beg || bj - 1 > pm.end) continue;
-                    const S *pH = arena + pm.off * 3;
-                    if ((S)(pH[bj - 1 - pm.beg] + s + ps) == Hj) {
-                        cur_op = 0x1f; hit = 1;
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 0, 1, id, bj - 1, &status);
-                        bi = p; --bj; id = jb.row_node_id[bi];
-                        ++n_aln; n_matched += is_match;
-                        break;
-                    }
-                }
-            }
-            if (!hit && (cur_op & 0x2)) { /* deletion */
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj < pm.beg || bj > pm.end) continue;
-                    const int poffc = bj - pm.beg;
-                    const int64_t pbw = pm.end - pm.beg + 1;
-                    const S *pH = arena + pm.off * 3;
-                    const S *pE1 = pH + pbw;
-                    if (cur_op & 0x1) {
-                        if (Hj == (S)(pE1[poffc] + ps)) {
-                            cur_op = ((S)(pH[poffc] - oe1) == pE1[poffc]) ? (0x1 | 0x18) : 0x2;
-                            hit = 1; dev_push_cigar(cig, &n_c, jb.cigar_cap, 2, 1, id, bj - 1, &status);
-                            bi = p; id = jb.row_node_id[bi];
-                            if (look_end) look_end = 0;
-                            break;
-                        }
-                    } else {
-                        if (E1j == (S)(pE1[poffc] - e1 + ps)) {
-                            cur_op = ((S)(pH[poffc] - oe1) == pE1[poffc]) ? (0x1 | 0x18) : 0x2;
-                            hit = 1; dev_push_cigar(cig, &n_c, jb.cigar_cap, 2, 1, id, bj - 1, &status);
-                            bi = p; id = jb.row_node_id[bi];
-                            if (look_end) look_end = 0;
-                            break;
-                        }
-                    }
-                }
-            }
-            if (!hit && (cur_op & 0x18)) { /* insertion */
-                if (cur_op & 0x1) {
-                    if (Hj == F1j) {
-                        if ((S)(Hjm1 - oe1) == F1j) { cur_op = 0x1 | 0x6; hit = 1; }
-                        else if ((S)(F1jm1 - e1) == F1j) { cur_op = 0x8; hit = 1; }
-                    }
-                } else {
-                    if ((S)(Hjm1 - oe1) == F1j) { cur_op = 0x1 | 0x6; hit = 1; }
-                    else if ((S)(F1jm1 - e1) == F1j) { cur_op = 0x8; hit = 1; }
-                }
-                if (hit) {
-                    dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, 1, id, bj - 1, &status);
-                    --bj;
-                    if (look_end) look_end = 0;
-                    ++n_aln;
-                }
-            }
-            if (!hit && (cur_op & 0x1)) {
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj - 1 < pm.beg || bj - 1 > pm.end) continue;
-                    const S *pH = arena + pm.off * 3;
-                    if ((S)(pH[bj - 1 - pm.beg] + s + ps) == Hj) {
-                        cur_op = 0x1f; hit = 1;
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 0, 1, id, bj - 1, &status);
-                        bi = p; --bj; id = jb.row_node_id[bi];
-                        ++n_aln; n_matched += is_match;
-                        look_end = 0;
-                        break;
-                    }
-                }
-            }
-            if (!hit) { status = ABAMD_JOB_BT_DEAD_END; break; }
-        }
-        if (status == ABAMD_JOB_OK && bj > 0)
-            dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, bj, -1, bj - 1, &status);
-        res->status = status;
-        res->n_cigar = n_c;
-        res->n_aln_bases = n_aln;
-        res->n_matched_bases = n_matched;
-        res->node_e = jb.row_node_id[best_i]; res->query_e = best_j - 1;
-        res->node_s = jb.row_node_id[start_i]; res->query_s = start_j - 1;
-    }
-}
-
-/* ------------------------------------------------------------------ */
-/* Linear-gap global kernel: one H plane.                              */
-/* Reference core simd_abpoa_lg_dp (abpoa_align_simd.c:727-815):       */
-/* H = max over preds of (preH[j-1]+q, preH[j]-e1), then an in-row     */
-/* max-plus insertion scan directly on H.                              */
-/* Backtrack: simd_abpoa_lg_backtrack (:116-194).                      */
-/* ------------------------------------------------------------------ */
-template <typename S>
-__global__ __launch_bounds__(WAVE * JOBS_PER_BLOCK, 7)
-void lg_global_kernel(const abamd_gpu_job_t *__restrict__ jobs,
-                      abamd_gpu_res_t *__restrict__ results, int n_jobs) {
-    const int wid = threadIdx.x / WAVE;
-    const int jid = blockIdx.x * JOBS_PER_BLOCK + wid;
-    const int lane = threadIdx.x % WAVE;
-
-    __shared__ int mat_lds[27 * 27];
-    constexpr int BMAX = BmaxOf<S>::v;
-    __shared__ S prev_lds[JOBS_PER_BLOCK][2][BMAX];
-    {
-        const int m0 = jobs[0].m;
-        const int *mat0 = jobs[0].mat;
-        for (int i = threadIdx.x; i < m0 * m0; i += WAVE * JOBS_PER_BLOCK)
-            mat_lds[i] = mat0[i];
-    }
-    __syncthreads();
-    if (jid >= n_jobs) return;
-    /* by VALUE: every field lives in registers (uniform loads become
-       s_loads into SGPRs) — a reference would re-load fields from global
-       memory inside the row loop because arena/steering stores could alias
-       the jobs array in the compiler's view */
-    const abamd_gpu_job_t jb = jobs[jid];
-    abamd_gpu_res_t *res = &results[jid];
-    abamd_row_meta_t *__restrict__ meta = (abamd_row_meta_t*)jb.row_meta;
-
-    const int qlen = jb.qlen, n_rows = jb.n_rows, w = jb.w, m = jb.m;
-    const S inf_min = (S)jb.inf_min;
-    const S e1 = (S)jb.e1;
-    const int local_mode = jb.align_mode == 1, extend_mode = jb.align_mode == 2;
-    int32_t run_best = jb.inf_min;
-    int run_best_i = 0, run_best_j = 0, run_best_remain = jb.max_remain[0];
-    int zdropped = 0;
-    const int end_remain = jb.max_remain[n_rows - 1];
-    S *arena = (S*)jb.arena;
-    const uint8_t *__restrict__ query = jb.query;
-
-    if (lane == 0) { res->status = ABAMD_JOB_OK; res->n_cigar = 0; }
-
-    for (int i = lane; i < n_rows; i += WAVE) {
-        jb.max_left[i] = jb.node_n_init;
-        jb.max_right[i] = 0;
-    }
-    if (lane == 0) { jb.max_left[0] = 0; jb.max_right[0] = 0; }
-    for (int k = jb.out_off[0] + lane; k < jb.out_off[1]; k += WAVE) {
-        int o = jb.out_idx[k];
-        jb.max_left[o] = 1; jb.max_right[o] = 1;
-    }
-
-    int buf_cur = 0;
-    int prev_ok = 0, prev_row = -1, prev_beg = 0, prev_end = -1;
-
-    /* first row (simd_abpoa_lg_first_dp, abpoa_align_simd.c:635-649) */
-    int64_t used;
-    {
-        int mr = jb.max_remain[0] - end_remain - 1;
-        int end0;
-        if (jb.banded) {
-            int t = jb.max_right[0] > qlen - mr ? jb.max_right[0] : qlen - mr;
-            end0 = (qlen < t + w) ? qlen : t + w;
-        } else end0 = qlen;
-        if (lane == 0) { meta[0].beg = 0; meta[0].end = end0; meta[0].off = 0; }
-        used = end0 + 1;
-        S *H = arena;
-        S *c = &prev_lds[wid][buf_cur][0];
-        const int fits = end0 + 1 <= BMAX;
-        for (int j = lane; j <= end0; j += WAVE) {
-            S hv = local_mode ? (S)0 : (S)(-jb.e1 * j);
-            H[j] = hv;
-            if (fits) c[j] = hv;
-        }
-        if (fits) { prev_ok = 1; prev_row = 0; prev_beg = 0; prev_end = end0; }
-        buf_cur ^= 1;
-    }
-
-    for (int r = 1; r < n_rows - 1; ++r) {
-        const int pk0 = jb.pre_off[r], pk1 = jb.pre_off[r + 1];
-        int beg, end;
-        {
-            int mr = jb.max_remain[r] - end_remain - 1;
-            if (jb.banded) {
-                int ml = jb.max_left[r], mrr = jb.max_right[r];
-                int lo = ml < qlen - mr ? ml : qlen - mr;
-                beg = lo - w; if (beg < 0) beg = 0;
-                int hi = mrr > qlen - mr ? mrr : qlen - mr;
-                end = hi + w; if (end > qlen) end = qlen;
-                int min_pre_beg = 0x7fffffff;
-                for (int k = pk0; k < pk1; ++k) {
-                    const int pidx = jb.pre_idx[k];
-                    int pb = (prev_ok && pidx == prev_row) ? prev_beg : meta[pidx].beg;
-                    if (pb < min_pre_beg) min_pre_beg = pb;
-                }
-                if (beg < min_pre_beg) beg = min_pre_beg;
-            } else { beg = 0; end = qlen; }
-        }
-        const int64_t bw = end - beg + 1;
-        if (used + bw > jb.arena_cap) { if (lane == 0) res->status = ABAMD_JOB_ARENA_OVERFLOW; return; }
-        const int64_t off = used;
-        if (lane == 0) { meta[r].beg = beg; meta[r].end = end; meta[r].off = off; }
-        used += bw;
-        S *H = arena + off;
-        const uint8_t base = jb.row_base[r];
-        const int *mrow = &mat_lds[base * m];
-        const int cache_fits = bw <= BMAX;
-        S *cw = &prev_lds[wid][buf_cur][0];
-        const S *cr = &prev_lds[wid][buf_cur ^ 1][0];
-
-        S carry_h = inf_min;
-        S lmax = inf_min; int lleft = -1, lright = -1;
-
-        for (int cs = beg; cs <= end; cs += WAVE) {
-            const int j = cs + lane;
-            const bool act = j <= end;
-            const S q = (S)((j == 0 || !act) ? 0 : mrow[query[j - 1]]);
-            S h = inf_min;
-            for (int k = pk0; k < pk1; ++k) {
-                const int p = jb.pre_idx[k];
-                const S ps = (S)jb.pre_ps[k];
-                if (prev_ok && p == prev_row) {
-                    if (act) {
-                        if (local_mode && j == 0) { S v = (S)(ps + q); if (v > h) h = v; }
-                        if (j - 1 >= prev_beg && j - 1 <= prev_end) {
-                            S v = (S)(cr[j - 1 - prev_beg] + ps + q);
-                            if (v > h) h = v;
-                        }
-                        if (j >= prev_beg && j <= prev_end) {
-                            S v = (S)(cr[j - prev_beg] + ps - e1);
-                            if (v > h) h = v;
-                        }
-                    }
-                    continue;
-                }
-                const abamd_row_meta_t pm = meta[p];
-                const S *__restrict__ pH = arena + pm.off;
-                if (act) {
-                    if (local_mode && j == 0) { S v = (S)(ps + q); if (v > h) h = v; }
-                    if (j - 1 >= pm.beg && j - 1 <= pm.end) {
-                        S v = (S)(pH[j - 1 - pm.beg] + ps + q);
-                        if (v > h) h = v;
-                    }
-                    if (j >= pm.beg && j <= pm.end) {
-                        S v = (S)(pH[j - pm.beg] + ps - e1);
-                        if (v > h) h = v;
-                    }
-                }
-            }
-            if (!act) h = inf_min;
-            /* in-row insertion scan on H with inter-chunk carry */
-            S hs = (S)__shfl_up((int)h, 1);
-            if (lane == 0) {
-                if (cs != beg) h = smax(h, (S)(carry_h - e1));
-            } else h = smax(h, (S)(hs - e1));
-            h = scan_maxplus(h, jb.e1, inf_min, lane);
-            carry_h = (S)__builtin_amdgcn_readlane((int)h, WAVE - 1);
-            if (local_mode) h = smax(h, (S)0); /* clamp AFTER the scan+carry */
-            if (act) {
-                H[j - beg] = h;
-                if (cache_fits) cw[j - beg] = h;
-                if (h > lmax) { lmax = h; lleft = j; lright = j; }
-                else if (h == lmax) { lright = j; }
-            }
-        }
-
-        if (cache_fits) { prev_ok = 1; prev_row = r; prev_beg = beg; prev_end = end; }
-        else prev_ok = 0;
-        buf_cur ^= 1;
-
-        if (jb.banded || local_mode || extend_mode) {
-            int mv = wave_red_max_i32((int)lmax);
-            int ll = ((int)lmax == mv && lleft >= 0) ? lleft : 0x7fffffff;
-            int rr = ((int)lmax == mv && lright >= 0) ? lright : -1;
-            ll = wave_red_min_i32(ll);
-            rr = wave_red_max_i32(rr);
-            if (local_mode) {
-                if (mv > run_best) { run_best = mv; run_best_i = r; run_best_j = ll; }
-            } else if (extend_mode) {
-                if (mv > run_best) {
-                    run_best = mv; run_best_i = r; run_best_j = rr;
-                    run_best_remain = jb.max_remain[r];
-                } else if (jb.zdrop > 0) {
-                    int delta = run_best_remain - jb.max_remain[r];
-                    int dd = delta - (rr - run_best_j); if (dd < 0) dd = -dd;
-                    if (run_best - mv > jb.zdrop + jb.e1 * dd) zdropped = 1;
-                }
-            }
-            if (!zdropped && jb.banded) {
-                for (int k = jb.out_off[r] + lane; k < jb.out_off[r + 1]; k += WAVE) {
-                    int o = jb.out_idx[k];
-                    if (rr + 1 > jb.max_right[o]) jb.max_right[o] = rr + 1;
-                    if (ll + 1 < jb.max_left[o]) jb.max_left[o] = ll + 1;
-                }
-            }
-            if (zdropped) break;
-        }
-    }
-
-    if (lane == 0) res->cells = used;
-    if (lane != 0) return;
-
-    int32_t best_score = run_best;
-    int best_i = run_best_i, best_j = run_best_j;
-    if (jb.align_mode == 0) {
-        best_score = jb.inf_min; best_i = 0; best_j = 0;
-        for (int k = jb.pre_off[n_rows - 1]; k < jb.pre_off[n_rows]; ++k) {
-            const int p = jb.pre_idx[k];
-            const abamd_row_meta_t pm = meta[p];
-            int e = pm.end < qlen ? pm.end : qlen;
-            const S *pH = arena + pm.off;
-            int32_t sc = (e >= pm.beg) ? (int32_t)pH[e - pm.beg] : jb.inf_min;
-            if (sc > best_score) { best_score = sc; best_i = p; best_j = e; }
-        }
-    }
-    res->best_score = best_score;
-    res->best_i = best_i; res->best_j = best_j;
-    if (!jb.ret_cigar) return;
-
-    { /* simd_abpoa_lg_backtrack (:116-194) */
-        int bi = best_i, bj = best_j, start_i = best_i, start_j = best_j;
-        int n_c = 0, status = ABAMD_JOB_OK;
-        int look_end = jb.put_gap_at_end, put_right = jb.put_gap_on_right;
-        int n_aln = 0, n_matched = 0;
-        uint64_t *cig = jb.cigar;
-        int id = jb.row_node_id[bi];
-        if (best_j < qlen) dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, qlen - best_j, -1, qlen - 1, &status);
-        while (bi > 0 && bj > 0 && status == ABAMD_JOB_OK) {
-            const abamd_row_meta_t bm = meta[bi];
-            const int rb = bm.beg, re = bm.end;
-            const S *H = arena + bm.off;
-            const S Hj = (bj >= rb && bj <= re) ? H[bj - rb] : inf_min;
-            const S Hjm1 = (bj - 1 >= rb && bj - 1 <= re) ? H[bj - 1 - rb] : inf_min;
-            if (local_mode && Hj == 0) break;
-            start_i = bi; start_j = bj;
-            const int pq0 = jb.pre_off[bi], pq1 = jb.pre_off[bi + 1];
-            const S s = (S)mat_lds[m * jb.row_base[bi] + query[bj - 1]];
-            const int is_match = jb.row_base[bi] == query[bj - 1];
-            int hit = 0;
-            if (put_right == 0 && look_end == 0) {
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj - 1 < pm.beg || bj - 1 > pm.end) continue;
-                    const S *pH = arena + pm.off;
-                    if ((S)(pH[bj - 1 - pm.beg] + s + ps) == Hj) {
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 0, 1, id, bj - 1, &status);
-                        bi = p; --bj; id = jb.row_node_id[bi]; hit = 1;
-                        ++n_aln; n_matched += is_match;
-                        break;
-                    }
-                }
-            }
-            if (!hit) { /* deletion */
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj < pm.beg || bj > pm.end) continue;
-                    const S *pH = arena + pm.off;
-                    if ((S)(pH[bj - pm.beg] - e1 + ps) == Hj) {
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 2, 1, id, bj - 1, &status);
-                        bi = p; id = jb.row_node_id[bi]; hit = 1;
-                        if (look_end) look_end = 0;
-                        break;
-                    }
-                }
-            }
-            if (!hit) { /* insertion */
-                if ((S)(Hjm1 - e1) == Hj) {
-                    dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, 1, id, bj - 1, &status);
-                    --bj;
-                    if (look_end) look_end = 0;
-                    hit = 1; ++n_aln;
-                }
-            }
-            if (!hit) {
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj - 1 < pm.beg || bj - 1 > pm.end) continue;
-                    const S *pH = arena + pm.off;
-                    if ((S)(pH[bj - 1 - pm.beg] + s + ps) == Hj) {
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 0, 1, id, bj - 1, &status);
-                        bi = p; --bj; id = jb.row_node_id[bi]; hit = 1;
-                        ++n_aln; n_matched += is_match;
-                        look_end = 0;
-                        break;
-                    }
-                }
-            }
-            if (!hit) { status = ABAMD_JOB_BT_DEAD_END; break; }
-        }
-        if (status == ABAMD_JOB_OK && bj > 0)
-            dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, bj, -1, bj - 1, &status);
-        res->status = status;
-        res->n_cigar = n_c;
-        res->n_aln_bases = n_aln;
-        res->n_matched_bases = n_matched;
-        res->node_e = jb.row_node_id[best_i]; res->query_e = best_j - 1;
-        res->node_s = jb.row_node_id[start_i]; res->query_s = start_j - 1;
-    }
-}
-
-/* ------------------------------------------------------------------ */
 /* Multi-wave affine kernel (3 planes H,E1,F1): same 8-waves-per-job   */
 /* design as the convex kernel; the F chain feeds from H BEFORE the E  */
 /* fold (simd_abpoa_ag_dp, abpoa_align_simd.c:817-933) and the stored  */
-/* E is inf_min when the insertion won the cell (SIMDSetIfEqual).      */
+/* E is inf_min when the insertion won the cell (SIMDSetIfEqual, :930).*/
+/* The H and E1 bands of the previous row stay in a double-buffered    */
+/* LDS cache; other predecessors, and rows wider than BMW, are read    */
+/* from the arena.                                                      */
 /* ------------------------------------------------------------------ */
 template <typename S>
 __global__ __launch_bounds__(MWT, 1)
@@ -1675,47 +1283,35 @@ void ag_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
     __shared__ int sc_red[3 * MWAVES];
     __shared__ S sc_carry[2];
 
+    /* by VALUE: every field lives in registers (uniform loads become
+       s_loads into SGPRs) — a reference would re-load fields from global
+       memory inside the row loop because arena/steering stores could alias
+       the jobs array in the compiler's view */
     const abamd_gpu_job_t jb = jobs[jid];
     abamd_gpu_res_t *res = &results[jid];
     abamd_row_meta_t *__restrict__ meta = (abamd_row_meta_t*)jb.row_meta;
 
-    const int qlen = jb.qlen, n_rows = jb.n_rows, w = jb.w, m = jb.m;
+    const int n_rows = jb.n_rows, m = jb.m;
     const S inf_min = (S)jb.inf_min;
     const S e1 = (S)jb.e1, oe1 = (S)jb.oe1;
-    const int local_mode = jb.align_mode == 1, extend_mode = jb.align_mode == 2;
-    int32_t run_best = jb.inf_min;
-    int run_best_i = 0, run_best_j = 0, run_best_remain = jb.max_remain[0];
-    int zdropped = 0;
+    const int local_mode = jb.align_mode == 1;
+    mw_best_t run = { jb.inf_min, 0, 0, jb.max_remain[0], 0 };
     const int end_remain = jb.max_remain[n_rows - 1];
     S *arena = (S*)jb.arena;
     const uint8_t *__restrict__ query = jb.query;
 
     for (int i = tid; i < m * m; i += MWT) mat_lds[i] = jb.mat[i];
     if (tid == 0) { res->status = ABAMD_JOB_OK; res->n_cigar = 0; }
-
-    for (int i = tid; i < n_rows; i += MWT) {
-        jb.max_left[i] = jb.node_n_init;
-        jb.max_right[i] = 0;
-    }
-    if (tid == 0) { jb.max_left[0] = 0; jb.max_right[0] = 0; }
-    for (int k = jb.out_off[0] + tid; k < jb.out_off[1]; k += MWT) {
-        int o = jb.out_idx[k];
-        jb.max_left[o] = 1; jb.max_right[o] = 1;
-    }
+    mw_steer_init(jb, tid);
     __syncthreads();
 
     int buf_cur = 0;
-    int prev_ok = 0, prev_row = -1, prev_beg = 0, prev_end = -1;
+    mw_prev_t prev = { 0, -1, 0, -1 };
 
     /* first row (simd_abpoa_ag_first_dp, abpoa_align_simd.c:651-667) */
     int64_t used;
     {
-        int mr = jb.max_remain[0] - end_remain - 1;
-        int end0;
-        if (jb.banded) {
-            int t = jb.max_right[0] > qlen - mr ? jb.max_right[0] : qlen - mr;
-            end0 = (qlen < t + w) ? qlen : t + w;
-        } else end0 = qlen;
+        const int end0 = mw_first_row_end(jb, end_remain);
         if (tid == 0) { meta[0].beg = 0; meta[0].end = end0; meta[0].off = 0; }
         int64_t bw = end0 + 1;
         used = bw;
@@ -1737,75 +1333,31 @@ void ag_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             H[j] = hv; E1[j] = e1v2;
             if (fits) { c[j] = hv; c[BMW + j] = e1v2; }
         }
-        if (fits) { prev_ok = 1; prev_row = 0; prev_beg = 0; prev_end = end0; }
+        if (fits) prev = mw_prev_t{ 1, 0, 0, end0 };
         buf_cur ^= 1;
         __syncthreads();
     }
 
-    int cur_pk0 = jb.pre_off[1];
-    int cur_pk1 = jb.pre_off[2 <= n_rows ? 2 : n_rows];
-    int cur_oo0 = jb.out_off[1];
-    int cur_oo1 = jb.out_off[2 <= n_rows ? 2 : n_rows];
-    int cur_remain = jb.max_remain[1];
-    int cur_ml_mem = jb.max_left[1];
-    int cur_mr_mem = jb.max_right[1];
-    int cur_pidx0 = jb.pre_idx[cur_pk0];
-    int cur_ps0 = jb.pre_ps[cur_pk0];
-    int push_ml = 0x7fffffff, push_mr = -0x7fffffff;
+    const bool rowmax = mw_needs_rowmax(jb);
+    mw_row_t nxt;
+    nxt.first(jb);
     for (int r = 1; r < n_rows - 1; ++r) {
-        const int pk0 = cur_pk0, pk1 = cur_pk1;
-        const int oo0 = cur_oo0, oo1 = cur_oo1;
-        const int row_remain = cur_remain;
-        const int pidx0 = cur_pidx0;
-        const S ps0 = (S)cur_ps0;
-        const int ml_eff = cur_ml_mem < push_ml ? cur_ml_mem : push_ml;
-        const int mr_eff = cur_mr_mem > push_mr ? cur_mr_mem : push_mr;
-        {
-            const int nr = r + 1;
-            cur_pk0 = pk1;
-            cur_pk1 = jb.pre_off[nr + 1];
-            cur_oo0 = oo1;
-            cur_oo1 = jb.out_off[nr + 1];
-            cur_remain = jb.max_remain[nr];
-            cur_ml_mem = jb.max_left[nr];
-            cur_mr_mem = jb.max_right[nr];
-            cur_pidx0 = jb.pre_idx[cur_pk0];
-            cur_ps0 = jb.pre_ps[cur_pk0];
-        }
+        const mw_row_t row = nxt;
+        nxt.advance(jb, r + 1);
+        const int pk0 = row.pk0, pk1 = row.pk1;
+        const S ps0 = (S)row.ps0;
         int beg, end;
-        {
-            int mr = row_remain - end_remain - 1;
-            if (jb.banded) {
-                int lo = ml_eff < qlen - mr ? ml_eff : qlen - mr;
-                beg = lo - w; if (beg < 0) beg = 0;
-                int hi = mr_eff > qlen - mr ? mr_eff : qlen - mr;
-                end = hi + w; if (end > qlen) end = qlen;
-                int min_pre_beg;
-                if (pk1 - pk0 == 1) {
-                    min_pre_beg = (prev_ok && pidx0 == prev_row) ? prev_beg : meta[pidx0].beg;
-                } else {
-                    min_pre_beg = 0x7fffffff;
-                    for (int k = pk0; k < pk1; ++k) {
-                        const int pidx = jb.pre_idx[k];
-                        int pb = (prev_ok && pidx == prev_row) ? prev_beg : meta[pidx].beg;
-                        if (pb < min_pre_beg) min_pre_beg = pb;
-                    }
-                }
-                if (beg < min_pre_beg) beg = min_pre_beg;
-            } else { beg = 0; end = qlen; }
-        }
+        mw_row_band(jb, meta, row, prev, end_remain, beg, end);
         const int64_t bw = end - beg + 1;
-        if (used + bw > jb.arena_cap) { if (tid == 0) res->status = ABAMD_JOB_ARENA_OVERFLOW; return; }
-        const int64_t off = used;
-        if (tid == 0) { meta[r].beg = beg; meta[r].end = end; meta[r].off = off; }
-        used += bw;
+        const int64_t off = mw_row_reserve(jb, meta, tid, r, beg, end, used);
+        if (off < 0) { if (tid == 0) res->status = ABAMD_JOB_ARENA_OVERFLOW; return; }
         S *H = arena + off * 3, *E1r = H + bw, *F1r = E1r + bw;
         const uint8_t base = jb.row_base[r];
         const int *mrow = &mat_lds[base * m];
         const int cache_fits = bw <= BMW;
         S *cw = &prev_lds[buf_cur][0];
         const S *cr = &prev_lds[buf_cur ^ 1][0];
-        const bool fast1 = (pk1 - pk0 == 1) && prev_ok && (pidx0 == prev_row);
+        const bool fast1 = (pk1 - pk0 == 1) && prev.ok && (row.pidx0 == prev.row);
 
         S carry_hm = inf_min, f1c = inf_min;
         S lmax = inf_min; int lleft = -1, lright = -1;
@@ -1817,27 +1369,27 @@ void ag_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             if (fast1) {
                 if (act) {
                     if (local_mode && j == 0) { if (ps0 > h) h = ps0; }
-                    if (j - 1 >= prev_beg && j - 1 <= prev_end) {
-                        S v = (S)(cr[j - 1 - prev_beg] + ps0);
+                    if (j - 1 >= prev.beg && j - 1 <= prev.end) {
+                        S v = (S)(cr[j - 1 - prev.beg] + ps0);
                         if (v > h) h = v;
                     }
-                    if (j >= prev_beg && j <= prev_end) {
-                        S v1 = (S)(cr[BMW + j - prev_beg] + ps0);
+                    if (j >= prev.beg && j <= prev.end) {
+                        S v1 = (S)(cr[BMW + j - prev.beg] + ps0);
                         if (v1 > e1v) e1v = v1;
                     }
                 }
             } else for (int k = pk0; k < pk1; ++k) {
                 const int p = jb.pre_idx[k];
                 const S ps = (S)jb.pre_ps[k];
-                if (prev_ok && p == prev_row) {
+                if (prev.ok && p == prev.row) {
                     if (act) {
                         if (local_mode && j == 0) { if (ps > h) h = ps; }
-                        if (j - 1 >= prev_beg && j - 1 <= prev_end) {
-                            S v = (S)(cr[j - 1 - prev_beg] + ps);
+                        if (j - 1 >= prev.beg && j - 1 <= prev.end) {
+                            S v = (S)(cr[j - 1 - prev.beg] + ps);
                             if (v > h) h = v;
                         }
-                        if (j >= prev_beg && j <= prev_end) {
-                            S v1 = (S)(cr[BMW + j - prev_beg] + ps);
+                        if (j >= prev.beg && j <= prev.end) {
+                            S v1 = (S)(cr[BMW + j - prev.beg] + ps);
                             if (v1 > e1v) e1v = v1;
                         }
                     }
@@ -1864,7 +1416,7 @@ void ag_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             if (!act) hm = inf_min;
 
             if (lane == WAVE - 1) sc_h[wv] = hm;
-            __syncthreads();
+            __syncthreads(); /* wave edges of hm */
             S hmshift = (S)__shfl_up((int)hm, 1);
             S c1;
             if (lane == 0) {
@@ -1877,7 +1429,7 @@ void ag_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             } else c1 = (S)(hmshift - oe1);
             S L1 = scan_maxplus(c1, jb.e1, inf_min, lane);
             if (lane == WAVE - 1) sc_f1[wv] = L1;
-            __syncthreads();
+            __syncthreads(); /* per-wave local scans */
             S f1 = L1;
             if (wv > 0) {
                 S C1 = sc_f1[0];
@@ -1901,212 +1453,104 @@ void ag_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             if (more && j == ss + MWT - 1) {
                 sc_carry[0] = hm; sc_carry[1] = f1;
             }
-            if (!more && (jb.banded || local_mode || extend_mode)) {
-                int mvw = wave_red_max_i32((int)lmax);
-                int llw = ((int)lmax == mvw && lleft >= 0) ? lleft : 0x7fffffff;
-                int rrw = ((int)lmax == mvw && lright >= 0) ? lright : -1;
-                llw = wave_red_min_i32(llw);
-                rrw = wave_red_max_i32(rrw);
-                if (lane == 0) {
-                    sc_red[wv] = mvw;
-                    sc_red[MWAVES + wv] = llw;
-                    sc_red[2 * MWAVES + wv] = rrw;
-                }
-            }
+            if (!more && rowmax)
+                mw_rowmax_publish(sc_red, wv, lane, lmax, lleft, lright);
             __syncthreads(); /* also orders cw writes before the next row's reads */
             if (more) { carry_hm = sc_carry[0]; f1c = sc_carry[1]; }
         }
 
-        if (cache_fits) { prev_ok = 1; prev_row = r; prev_beg = beg; prev_end = end; }
-        else prev_ok = 0;
+        if (cache_fits) prev = mw_prev_t{ 1, r, beg, end };
+        else prev.ok = 0;
         buf_cur ^= 1;
 
-        if (jb.banded || local_mode || extend_mode) {
-            int mv = sc_red[0], ll = sc_red[MWAVES], rr = sc_red[2 * MWAVES];
-            #pragma unroll
-            for (int ww = 1; ww < MWAVES; ++ww) {
-                int m2 = sc_red[ww];
-                if (m2 > mv) { mv = m2; ll = sc_red[MWAVES + ww]; rr = sc_red[2 * MWAVES + ww]; }
-                else if (m2 == mv) {
-                    if (sc_red[MWAVES + ww] < ll) ll = sc_red[MWAVES + ww];
-                    if (sc_red[2 * MWAVES + ww] > rr) rr = sc_red[2 * MWAVES + ww];
-                }
-            }
-            if (local_mode) {
-                if (mv > run_best) { run_best = mv; run_best_i = r; run_best_j = ll; }
-            } else if (extend_mode) {
-                if (mv > run_best) {
-                    run_best = mv; run_best_i = r; run_best_j = rr;
-                    run_best_remain = row_remain;
-                } else if (jb.zdrop > 0) {
-                    int delta = run_best_remain - row_remain;
-                    int dd = delta - (rr - run_best_j); if (dd < 0) dd = -dd;
-                    if (run_best - mv > jb.zdrop + jb.e1 * dd) zdropped = 1;
-                }
-            }
-            push_ml = 0x7fffffff; push_mr = -0x7fffffff;
-            if (!zdropped && jb.banded) {
-                for (int k = oo0; k < oo1; ++k) {
-                    int o = jb.out_idx[k];
-                    if (o == r + 1) {
-                        if (rr + 1 > push_mr) push_mr = rr + 1;
-                        if (ll + 1 < push_ml) push_ml = ll + 1;
-                    } else {
-                        if (rr + 1 > jb.max_right[o]) jb.max_right[o] = rr + 1;
-                        if (ll + 1 < jb.max_left[o]) jb.max_left[o] = ll + 1;
-                    }
-                }
-            }
-            if (zdropped) break;
-        } else {
-            push_ml = 0x7fffffff; push_mr = -0x7fffffff;
-        }
+        if (mw_row_close(jb, sc_red, row, r, run, nxt)) break;
     }
 
     __syncthreads();
     if (tid == 0) res->cells = used;
     if (tid != 0) return;
 
-    int32_t best_score = run_best;
-    int best_i = run_best_i, best_j = run_best_j;
-    if (jb.align_mode == 0) {
-        best_score = jb.inf_min; best_i = 0; best_j = 0;
-        for (int k = jb.pre_off[n_rows - 1]; k < jb.pre_off[n_rows]; ++k) {
-            const int p = jb.pre_idx[k];
-            const abamd_row_meta_t pm = meta[p];
-            int e = pm.end < qlen ? pm.end : qlen;
-            const S *pH = arena + pm.off * 3;
-            int32_t sc = (e >= pm.beg) ? (int32_t)pH[e - pm.beg] : jb.inf_min;
-            if (sc > best_score) { best_score = sc; best_i = p; best_j = e; }
-        }
-    }
+    int32_t best_score;
+    int best_i, best_j;
+    mw_final_best<S>(jb, run, 3, best_score, best_i, best_j);
     res->best_score = best_score;
     res->best_i = best_i; res->best_j = best_j;
     if (!jb.ret_cigar) return;
-    { /* simd_abpoa_ag_backtrack (:196-307) */
-        int bi = best_i, bj = best_j, start_i = best_i, start_j = best_j;
-        int cur_op = 0x1f, n_c = 0, status = ABAMD_JOB_OK;
-        int look_end = jb.put_gap_at_end, put_right = jb.put_gap_on_right;
-        int n_aln = 0, n_matched = 0;
-        uint64_t *cig = jb.cigar;
-        int id = jb.row_node_id[bi];
-        if (best_j < qlen) dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, qlen - best_j, -1, qlen - 1, &status);
-        while (bi > 0 && bj > 0 && status == ABAMD_JOB_OK) {
-            const abamd_row_meta_t bm = meta[bi];
-            const int rb = bm.beg, re = bm.end;
-            const int64_t bw = re - rb + 1;
-            const S *H = arena + bm.off * 3;
-            const S *E1r = H + bw, *F1r = E1r + bw;
-            const S Hj = (bj >= rb && bj <= re) ? H[bj - rb] : inf_min;
-            const S Hjm1 = (bj - 1 >= rb && bj - 1 <= re) ? H[bj - 1 - rb] : inf_min;
-            const S E1j = (bj >= rb && bj <= re) ? E1r[bj - rb] : inf_min;
-            const S F1j = (bj >= rb && bj <= re) ? F1r[bj - rb] : inf_min;
-            const S F1jm1 = (bj - 1 >= rb && bj - 1 <= re) ? F1r[bj - 1 - rb] : inf_min;
-            if (local_mode && Hj == 0) break;
-            start_i = bi; start_j = bj;
-            const int pq0 = jb.pre_off[bi], pq1 = jb.pre_off[bi + 1];
-            const S s = (S)mat_lds[m * jb.row_base[bi] + query[bj - 1]];
-            const int is_match = jb.row_base[bi] == query[bj - 1];
-            int hit = 0;
-            if (put_right == 0 && look_end == 0 && (cur_op & 0x1)) {
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj - 1 < pm.beg || bj - 1 > pm.end) continue;
-                    const S *pH = arena + pm.off * 3;
-                    if ((S)(pH[bj - 1 - pm.beg] + s + ps) == Hj) {
-                        cur_op = 0x1f; hit = 1;
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 0, 1, id, bj - 1, &status);
-                        bi = p; --bj; id = jb.row_node_id[bi];
-                        ++n_aln; n_matched += is_match;
-                        break;
-                    }
-                }
-            }
-            if (!hit && (cur_op & 0x2)) { /* deletion */
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj < pm.beg || bj > pm.end) continue;
-                    const int poffc = bj - pm.beg;
-                    const int64_t pbw = pm.end - pm.beg + 1;
-                    const S *pH = arena + pm.off * 3;
-                    const S *pE1 = pH + pbw;
-                    if (cur_op & 0x1) {
-                        if (Hj == (S)(pE1[poffc] + ps)) {
-                            cur_op = ((S)(pH[poffc] - oe1) == pE1[poffc]) ? (0x1 | 0x18) : 0x2;
-                            hit = 1; dev_push_cigar(cig, &n_c, jb.cigar_cap, 2, 1, id, bj - 1, &status);
-                            bi = p; id = jb.row_node_id[bi];
-                            if (look_end) look_end = 0;
-                            break;
-                        }
-                    } else {
-                        if (E1j == (S)(pE1[poffc] - e1 + ps)) {
-                            cur_op = ((S)(pH[poffc] - oe1) == pE1[poffc]) ? (0x1 | 0x18) : 0x2;
-                            hit = 1; dev_push_cigar(cig, &n_c, jb.cigar_cap, 2, 1, id, bj - 1, &status);
-                            bi = p; id = jb.row_node_id[bi];
-                            if (look_end) look_end = 0;
-                            break;
-                        }
-                    }
-                }
-            }
-            if (!hit && (cur_op & 0x18)) { /* insertion */
-                if (cur_op & 0x1) {
-                    if (Hj == F1j) {
-                        if ((S)(Hjm1 - oe1) == F1j) { cur_op = 0x1 | 0x6; hit = 1; }
-                        else if ((S)(F1jm1 - e1) == F1j) { cur_op = 0x8; hit = 1; }
-                    }
-                } else {
-                    if ((S)(Hjm1 - oe1) == F1j) { cur_op = 0x1 | 0x6; hit = 1; }
-                    else if ((S)(F1jm1 - e1) == F1j) { cur_op = 0x8; hit = 1; }
-                }
-                if (hit) {
-                    dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, 1, id, bj - 1, &status);
-                    --bj;
-                    if (look_end) look_end = 0;
-                    ++n_aln;
-                }
-            }
-            if (!hit && (cur_op & 0x1)) {
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj - 1 < pm.beg || bj - 1 > pm.end) continue;
-                    const S *pH = arena + pm.off * 3;
-                    if ((S)(pH[bj - 1 - pm.beg] + s + ps) == Hj) {
-                        cur_op = 0x1f; hit = 1;
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 0, 1, id, bj - 1, &status);
-                        bi = p; --bj; id = jb.row_node_id[bi];
-                        ++n_aln; n_matched += is_match;
-                        look_end = 0;
-                        break;
-                    }
-                }
-            }
-            if (!hit) { status = ABAMD_JOB_BT_DEAD_END; break; }
-        }
-        if (status == ABAMD_JOB_OK && bj > 0)
-            dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, bj, -1, bj - 1, &status);
-        res->status = status;
-        res->n_cigar = n_c;
-        res->n_aln_bases = n_aln;
-        res->n_matched_bases = n_matched;
-        res->node_e = jb.row_node_id[best_i]; res->query_e = best_j - 1;
-        res->node_s = jb.row_node_id[start_i]; res->query_s = start_j - 1;
-    }
-}
 
+    /* simd_abpoa_ag_backtrack (:196-307) */
+    mw_walk_t wk = mw_walk_begin(jb, best_i, best_j);
+    int cur_op = 0x1f;
+    while (wk.bi > 0 && wk.bj > 0 && wk.status == ABAMD_JOB_OK) {
+        const int bi = wk.bi, bj = wk.bj; /* the cell this step leaves */
+        const abamd_row_meta_t bm = meta[bi];
+        const int rb = bm.beg, re = bm.end;
+        const int64_t bw = re - rb + 1;
+        const S *H = arena + bm.off * 3;
+        const S *E1r = H + bw, *F1r = E1r + bw;
+        const S Hj = (bj >= rb && bj <= re) ? H[bj - rb] : inf_min;
+        const S Hjm1 = (bj - 1 >= rb && bj - 1 <= re) ? H[bj - 1 - rb] : inf_min;
+        const S E1j = (bj >= rb && bj <= re) ? E1r[bj - rb] : inf_min;
+        const S F1j = (bj >= rb && bj <= re) ? F1r[bj - rb] : inf_min;
+        const S F1jm1 = (bj - 1 >= rb && bj - 1 <= re) ? F1r[bj - 1 - rb] : inf_min;
+        if (local_mode && Hj == 0) break;
+        wk.start_i = bi; wk.start_j = bj;
+        const int pq0 = jb.pre_off[bi], pq1 = jb.pre_off[bi + 1];
+        const S s = (S)mat_lds[m * jb.row_base[bi] + query[bj - 1]];
+        const int is_match = jb.row_base[bi] == query[bj - 1];
+        int hit = 0;
+        if (wk.put_right == 0 && wk.look_end == 0 && (cur_op & 0x1)) {
+            hit = mw_walk_match<S>(jb, wk, 3, pq0, pq1, s, is_match, Hj);
+            if (hit) cur_op = 0x1f;
+        }
+        if (!hit && (cur_op & 0x2)) { /* deletion: entered from H, or E extended */
+            for (int k = pq0; k < pq1; ++k) {
+                const int p = jb.pre_idx[k];
+                const S ps = (S)jb.pre_ps[k];
+                const abamd_row_meta_t pm = meta[p];
+                if (bj < pm.beg || bj > pm.end) continue;
+                const int poffc = bj - pm.beg;
+                const int64_t pbw = pm.end - pm.beg + 1;
+                const S *pH = arena + pm.off * 3;
+                const S *pE1 = pH + pbw;
+                if ((cur_op & 0x1) ? Hj == (S)(pE1[poffc] + ps)
+                                   : E1j == (S)(pE1[poffc] - e1 + ps)) {
+                    cur_op = ((S)(pH[poffc] - oe1) == pE1[poffc]) ? (0x1 | 0x18) : 0x2;
+                    hit = 1;
+                    dev_push_cigar(jb.cigar, &wk.n_c, jb.cigar_cap, 2, 1, wk.id, bj - 1, &wk.status);
+                    wk.bi = p; wk.id = jb.row_node_id[p];
+                    wk.look_end = 0;
+                    break;
+                }
+            }
+        }
+        if (!hit && (cur_op & 0x18)) { /* insertion */
+            if (!(cur_op & 0x1) || Hj == F1j) {
+                if ((S)(Hjm1 - oe1) == F1j) { cur_op = 0x1 | 0x6; hit = 1; }
+                else if ((S)(F1jm1 - e1) == F1j) { cur_op = 0x8; hit = 1; }
+            }
+            if (hit) {
+                dev_push_cigar(jb.cigar, &wk.n_c, jb.cigar_cap, 1, 1, wk.id, bj - 1, &wk.status);
+                --wk.bj;
+                wk.look_end = 0;
+                ++wk.n_aln;
+            }
+        }
+        if (!hit && (cur_op & 0x1)) {
+            hit = mw_walk_match<S>(jb, wk, 3, pq0, pq1, s, is_match, Hj);
+            if (hit) { cur_op = 0x1f; wk.look_end = 0; }
+        }
+        if (!hit) { wk.status = ABAMD_JOB_BT_DEAD_END; break; }
+    }
+    mw_walk_end(jb, res, wk, best_i, best_j);
+}
 
 /* ------------------------------------------------------------------ */
 /* Multi-wave linear kernel (1 plane): candidates carry the query score */
 /* and the deletion term, then the insertion max-plus scan runs on H    */
-/* itself (simd_abpoa_lg_dp, abpoa_align_simd.c:727-815); the local     */
-/* clamp applies AFTER the scan and the cross-wave carries are          */
-/* PRE-clamp, exactly like the one-wave kernel's readlane carry.        */
+/* itself (simd_abpoa_lg_dp, abpoa_align_simd.c:727-815). The local     */
+/* clamp applies AFTER the scan, and every carry (between waves and     */
+/* between superchunks) is the PRE-clamp scan value: the reference      */
+/* clamps a row only once its whole insertion chain has run (:814).     */
 /* ------------------------------------------------------------------ */
 template <typename S>
 __global__ __launch_bounds__(MWT, 1)
@@ -2123,47 +1567,32 @@ void lg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
     __shared__ int sc_red[3 * MWAVES];
     __shared__ S sc_carry[1];
 
+    /* by VALUE, for the reason given in the affine kernel */
     const abamd_gpu_job_t jb = jobs[jid];
     abamd_gpu_res_t *res = &results[jid];
     abamd_row_meta_t *__restrict__ meta = (abamd_row_meta_t*)jb.row_meta;
 
-    const int qlen = jb.qlen, n_rows = jb.n_rows, w = jb.w, m = jb.m;
+    const int n_rows = jb.n_rows, m = jb.m;
     const S inf_min = (S)jb.inf_min;
     const S e1 = (S)jb.e1;
-    const int local_mode = jb.align_mode == 1, extend_mode = jb.align_mode == 2;
-    int32_t run_best = jb.inf_min;
-    int run_best_i = 0, run_best_j = 0, run_best_remain = jb.max_remain[0];
-    int zdropped = 0;
+    const int local_mode = jb.align_mode == 1;
+    mw_best_t run = { jb.inf_min, 0, 0, jb.max_remain[0], 0 };
     const int end_remain = jb.max_remain[n_rows - 1];
     S *arena = (S*)jb.arena;
     const uint8_t *__restrict__ query = jb.query;
 
     for (int i = tid; i < m * m; i += MWT) mat_lds[i] = jb.mat[i];
     if (tid == 0) { res->status = ABAMD_JOB_OK; res->n_cigar = 0; }
-
-    for (int i = tid; i < n_rows; i += MWT) {
-        jb.max_left[i] = jb.node_n_init;
-        jb.max_right[i] = 0;
-    }
-    if (tid == 0) { jb.max_left[0] = 0; jb.max_right[0] = 0; }
-    for (int k = jb.out_off[0] + tid; k < jb.out_off[1]; k += MWT) {
-        int o = jb.out_idx[k];
-        jb.max_left[o] = 1; jb.max_right[o] = 1;
-    }
+    mw_steer_init(jb, tid);
     __syncthreads();
 
     int buf_cur = 0;
-    int prev_ok = 0, prev_row = -1, prev_beg = 0, prev_end = -1;
+    mw_prev_t prev = { 0, -1, 0, -1 };
 
     /* first row (simd_abpoa_lg_first_dp, abpoa_align_simd.c:635-649) */
     int64_t used;
     {
-        int mr = jb.max_remain[0] - end_remain - 1;
-        int end0;
-        if (jb.banded) {
-            int t = jb.max_right[0] > qlen - mr ? jb.max_right[0] : qlen - mr;
-            end0 = (qlen < t + w) ? qlen : t + w;
-        } else end0 = qlen;
+        const int end0 = mw_first_row_end(jb, end_remain);
         if (tid == 0) { meta[0].beg = 0; meta[0].end = end0; meta[0].off = 0; }
         used = end0 + 1;
         S *H = arena;
@@ -2174,75 +1603,31 @@ void lg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             H[j] = hv;
             if (fits) c[j] = hv;
         }
-        if (fits) { prev_ok = 1; prev_row = 0; prev_beg = 0; prev_end = end0; }
+        if (fits) prev = mw_prev_t{ 1, 0, 0, end0 };
         buf_cur ^= 1;
         __syncthreads();
     }
 
-    int cur_pk0 = jb.pre_off[1];
-    int cur_pk1 = jb.pre_off[2 <= n_rows ? 2 : n_rows];
-    int cur_oo0 = jb.out_off[1];
-    int cur_oo1 = jb.out_off[2 <= n_rows ? 2 : n_rows];
-    int cur_remain = jb.max_remain[1];
-    int cur_ml_mem = jb.max_left[1];
-    int cur_mr_mem = jb.max_right[1];
-    int cur_pidx0 = jb.pre_idx[cur_pk0];
-    int cur_ps0 = jb.pre_ps[cur_pk0];
-    int push_ml = 0x7fffffff, push_mr = -0x7fffffff;
+    const bool rowmax = mw_needs_rowmax(jb);
+    mw_row_t nxt;
+    nxt.first(jb);
     for (int r = 1; r < n_rows - 1; ++r) {
-        const int pk0 = cur_pk0, pk1 = cur_pk1;
-        const int oo0 = cur_oo0, oo1 = cur_oo1;
-        const int row_remain = cur_remain;
-        const int pidx0 = cur_pidx0;
-        const S ps0 = (S)cur_ps0;
-        const int ml_eff = cur_ml_mem < push_ml ? cur_ml_mem : push_ml;
-        const int mr_eff = cur_mr_mem > push_mr ? cur_mr_mem : push_mr;
-        {
-            const int nr = r + 1;
-            cur_pk0 = pk1;
-            cur_pk1 = jb.pre_off[nr + 1];
-            cur_oo0 = oo1;
-            cur_oo1 = jb.out_off[nr + 1];
-            cur_remain = jb.max_remain[nr];
-            cur_ml_mem = jb.max_left[nr];
-            cur_mr_mem = jb.max_right[nr];
-            cur_pidx0 = jb.pre_idx[cur_pk0];
-            cur_ps0 = jb.pre_ps[cur_pk0];
-        }
+        const mw_row_t row = nxt;
+        nxt.advance(jb, r + 1);
+        const int pk0 = row.pk0, pk1 = row.pk1;
+        const S ps0 = (S)row.ps0;
         int beg, end;
-        {
-            int mr = row_remain - end_remain - 1;
-            if (jb.banded) {
-                int lo = ml_eff < qlen - mr ? ml_eff : qlen - mr;
-                beg = lo - w; if (beg < 0) beg = 0;
-                int hi = mr_eff > qlen - mr ? mr_eff : qlen - mr;
-                end = hi + w; if (end > qlen) end = qlen;
-                int min_pre_beg;
-                if (pk1 - pk0 == 1) {
-                    min_pre_beg = (prev_ok && pidx0 == prev_row) ? prev_beg : meta[pidx0].beg;
-                } else {
-                    min_pre_beg = 0x7fffffff;
-                    for (int k = pk0; k < pk1; ++k) {
-                        const int pidx = jb.pre_idx[k];
-                        int pb = (prev_ok && pidx == prev_row) ? prev_beg : meta[pidx].beg;
-                        if (pb < min_pre_beg) min_pre_beg = pb;
-                    }
-                }
-                if (beg < min_pre_beg) beg = min_pre_beg;
-            } else { beg = 0; end = qlen; }
-        }
+        mw_row_band(jb, meta, row, prev, end_remain, beg, end);
         const int64_t bw = end - beg + 1;
-        if (used + bw > jb.arena_cap) { if (tid == 0) res->status = ABAMD_JOB_ARENA_OVERFLOW; return; }
-        const int64_t off = used;
-        if (tid == 0) { meta[r].beg = beg; meta[r].end = end; meta[r].off = off; }
-        used += bw;
+        const int64_t off = mw_row_reserve(jb, meta, tid, r, beg, end, used);
+        if (off < 0) { if (tid == 0) res->status = ABAMD_JOB_ARENA_OVERFLOW; return; }
         S *H = arena + off;
         const uint8_t base = jb.row_base[r];
         const int *mrow = &mat_lds[base * m];
         const int cache_fits = bw <= BMW;
         S *cw = &prev_lds[buf_cur][0];
         const S *cr = &prev_lds[buf_cur ^ 1][0];
-        const bool fast1 = (pk1 - pk0 == 1) && prev_ok && (pidx0 == prev_row);
+        const bool fast1 = (pk1 - pk0 == 1) && prev.ok && (row.pidx0 == prev.row);
 
         S carry_h = inf_min;                 /* PRE-clamp scan value at ss-1 */
         S lmax = inf_min; int lleft = -1, lright = -1;
@@ -2255,27 +1640,27 @@ void lg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             if (fast1) {
                 if (act) {
                     if (local_mode && j == 0) { S v = (S)(ps0 + q); if (v > h) h = v; }
-                    if (j - 1 >= prev_beg && j - 1 <= prev_end) {
-                        S v = (S)(cr[j - 1 - prev_beg] + ps0 + q);
+                    if (j - 1 >= prev.beg && j - 1 <= prev.end) {
+                        S v = (S)(cr[j - 1 - prev.beg] + ps0 + q);
                         if (v > h) h = v;
                     }
-                    if (j >= prev_beg && j <= prev_end) {
-                        S v = (S)(cr[j - prev_beg] + ps0 - e1);
+                    if (j >= prev.beg && j <= prev.end) {
+                        S v = (S)(cr[j - prev.beg] + ps0 - e1);
                         if (v > h) h = v;
                     }
                 }
             } else for (int k = pk0; k < pk1; ++k) {
                 const int p = jb.pre_idx[k];
                 const S ps = (S)jb.pre_ps[k];
-                if (prev_ok && p == prev_row) {
+                if (prev.ok && p == prev.row) {
                     if (act) {
                         if (local_mode && j == 0) { S v = (S)(ps + q); if (v > h) h = v; }
-                        if (j - 1 >= prev_beg && j - 1 <= prev_end) {
-                            S v = (S)(cr[j - 1 - prev_beg] + ps + q);
+                        if (j - 1 >= prev.beg && j - 1 <= prev.end) {
+                            S v = (S)(cr[j - 1 - prev.beg] + ps + q);
                             if (v > h) h = v;
                         }
-                        if (j >= prev_beg && j <= prev_end) {
-                            S v = (S)(cr[j - prev_beg] + ps - e1);
+                        if (j >= prev.beg && j <= prev.end) {
+                            S v = (S)(cr[j - prev.beg] + ps - e1);
                             if (v > h) h = v;
                         }
                     }
@@ -2297,12 +1682,12 @@ void lg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             }
             if (!act) h = inf_min;
 
-            /* insertion scan ON H: per-wave local scan + cross-wave carry
-             * (the merged-candidate + scan form of the one-wave kernel
-             * regroups to exactly this under wrapping arithmetic) */
+            /* insertion scan ON H: per-wave local scan + cross-wave carry.
+             * Splitting the row's one max-plus chain at the wave edges is
+             * exact: the decays regroup under wrapping arithmetic. */
             S L1 = scan_maxplus(h, jb.e1, inf_min, lane);
             if (lane == WAVE - 1) sc_f1[wv] = L1;
-            __syncthreads();
+            __syncthreads(); /* per-wave local scans */
             S hsc = L1;
             {
                 S C1 = carry_h;
@@ -2322,224 +1707,94 @@ void lg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
             }
             const bool more = ss + MWT <= end;
             if (more && j == ss + MWT - 1) sc_carry[0] = hsc; /* PRE-clamp */
-            if (!more && (jb.banded || local_mode || extend_mode)) {
-                int mvw = wave_red_max_i32((int)lmax);
-                int llw = ((int)lmax == mvw && lleft >= 0) ? lleft : 0x7fffffff;
-                int rrw = ((int)lmax == mvw && lright >= 0) ? lright : -1;
-                llw = wave_red_min_i32(llw);
-                rrw = wave_red_max_i32(rrw);
-                if (lane == 0) {
-                    sc_red[wv] = mvw;
-                    sc_red[MWAVES + wv] = llw;
-                    sc_red[2 * MWAVES + wv] = rrw;
-                }
-            }
+            if (!more && rowmax)
+                mw_rowmax_publish(sc_red, wv, lane, lmax, lleft, lright);
             __syncthreads(); /* also orders cw writes before the next row's reads */
             if (more) carry_h = sc_carry[0];
         }
 
-        if (cache_fits) { prev_ok = 1; prev_row = r; prev_beg = beg; prev_end = end; }
-        else prev_ok = 0;
+        if (cache_fits) prev = mw_prev_t{ 1, r, beg, end };
+        else prev.ok = 0;
         buf_cur ^= 1;
 
-        if (jb.banded || local_mode || extend_mode) {
-            int mv = sc_red[0], ll = sc_red[MWAVES], rr = sc_red[2 * MWAVES];
-            #pragma unroll
-            for (int ww = 1; ww < MWAVES; ++ww) {
-                int m2 = sc_red[ww];
-                if (m2 > mv) { mv = m2; ll = sc_red[MWAVES + ww]; rr = sc_red[2 * MWAVES + ww]; }
-                else if (m2 == mv) {
-                    if (sc_red[MWAVES + ww] < ll) ll = sc_red[MWAVES + ww];
-                    if (sc_red[2 * MWAVES + ww] > rr) rr = sc_red[2 * MWAVES + ww];
-                }
-            }
-            if (local_mode) {
-                if (mv > run_best) { run_best = mv; run_best_i = r; run_best_j = ll; }
-            } else if (extend_mode) {
-                if (mv > run_best) {
-                    run_best = mv; run_best_i = r; run_best_j = rr;
-                    run_best_remain = row_remain;
-                } else if (jb.zdrop > 0) {
-                    int delta = run_best_remain - row_remain;
-                    int dd = delta - (rr - run_best_j); if (dd < 0) dd = -dd;
-                    if (run_best - mv > jb.zdrop + jb.e1 * dd) zdropped = 1;
-                }
-            }
-            push_ml = 0x7fffffff; push_mr = -0x7fffffff;
-            if (!zdropped && jb.banded) {
-                for (int k = oo0; k < oo1; ++k) {
-                    int o = jb.out_idx[k];
-                    if (o == r + 1) {
-                        if (rr + 1 > push_mr) push_mr = rr + 1;
-                        if (ll + 1 < push_ml) push_ml = ll + 1;
-                    } else {
-                        if (rr + 1 > jb.max_right[o]) jb.max_right[o] = rr + 1;
-                        if (ll + 1 < jb.max_left[o]) jb.max_left[o] = ll + 1;
-                    }
-                }
-            }
-            if (zdropped) break;
-        } else {
-            push_ml = 0x7fffffff; push_mr = -0x7fffffff;
-        }
+        if (mw_row_close(jb, sc_red, row, r, run, nxt)) break;
     }
 
     __syncthreads();
     if (tid == 0) res->cells = used;
     if (tid != 0) return;
 
-    int32_t best_score = run_best;
-    int best_i = run_best_i, best_j = run_best_j;
-    if (jb.align_mode == 0) {
-        best_score = jb.inf_min; best_i = 0; best_j = 0;
-        for (int k = jb.pre_off[n_rows - 1]; k < jb.pre_off[n_rows]; ++k) {
-            const int p = jb.pre_idx[k];
-            const abamd_row_meta_t pm = meta[p];
-            int e = pm.end < qlen ? pm.end : qlen;
-            const S *pH = arena + pm.off;
-            int32_t sc = (e >= pm.beg) ? (int32_t)pH[e - pm.beg] : jb.inf_min;
-            if (sc > best_score) { best_score = sc; best_i = p; best_j = e; }
-        }
-    }
+    int32_t best_score;
+    int best_i, best_j;
+    mw_final_best<S>(jb, run, 1, best_score, best_i, best_j);
     res->best_score = best_score;
     res->best_i = best_i; res->best_j = best_j;
     if (!jb.ret_cigar) return;
 
-    { /* simd_abpoa_lg_backtrack (:116-194) */
-        int bi = best_i, bj = best_j, start_i = best_i, start_j = best_j;
-        int n_c = 0, status = ABAMD_JOB_OK;
-        int look_end = jb.put_gap_at_end, put_right = jb.put_gap_on_right;
-        int n_aln = 0, n_matched = 0;
-        uint64_t *cig = jb.cigar;
-        int id = jb.row_node_id[bi];
-        if (best_j < qlen) dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, qlen - best_j, -1, qlen - 1, &status);
-        while (bi > 0 && bj > 0 && status == ABAMD_JOB_OK) {
-            const abamd_row_meta_t bm = meta[bi];
-            const int rb = bm.beg, re = bm.end;
-            const S *H = arena + bm.off;
-            const S Hj = (bj >= rb && bj <= re) ? H[bj - rb] : inf_min;
-            const S Hjm1 = (bj - 1 >= rb && bj - 1 <= re) ? H[bj - 1 - rb] : inf_min;
-            if (local_mode && Hj == 0) break;
-            start_i = bi; start_j = bj;
-            const int pq0 = jb.pre_off[bi], pq1 = jb.pre_off[bi + 1];
-            const S s = (S)mat_lds[m * jb.row_base[bi] + query[bj - 1]];
-            const int is_match = jb.row_base[bi] == query[bj - 1];
-            int hit = 0;
-            if (put_right == 0 && look_end == 0) {
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj - 1 < pm.beg || bj - 1 > pm.end) continue;
-                    const S *pH = arena + pm.off;
-                    if ((S)(pH[bj - 1 - pm.beg] + s + ps) == Hj) {
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 0, 1, id, bj - 1, &status);
-                        bi = p; --bj; id = jb.row_node_id[bi]; hit = 1;
-                        ++n_aln; n_matched += is_match;
-                        break;
-                    }
+    /* simd_abpoa_lg_backtrack (:116-194) */
+    mw_walk_t wk = mw_walk_begin(jb, best_i, best_j);
+    while (wk.bi > 0 && wk.bj > 0 && wk.status == ABAMD_JOB_OK) {
+        const int bi = wk.bi, bj = wk.bj; /* the cell this step leaves */
+        const abamd_row_meta_t bm = meta[bi];
+        const int rb = bm.beg, re = bm.end;
+        const S *H = arena + bm.off;
+        const S Hj = (bj >= rb && bj <= re) ? H[bj - rb] : inf_min;
+        const S Hjm1 = (bj - 1 >= rb && bj - 1 <= re) ? H[bj - 1 - rb] : inf_min;
+        if (local_mode && Hj == 0) break;
+        wk.start_i = bi; wk.start_j = bj;
+        const int pq0 = jb.pre_off[bi], pq1 = jb.pre_off[bi + 1];
+        const S s = (S)mat_lds[m * jb.row_base[bi] + query[bj - 1]];
+        const int is_match = jb.row_base[bi] == query[bj - 1];
+        int hit = 0;
+        if (wk.put_right == 0 && wk.look_end == 0)
+            hit = mw_walk_match<S>(jb, wk, 1, pq0, pq1, s, is_match, Hj);
+        if (!hit) { /* deletion */
+            for (int k = pq0; k < pq1; ++k) {
+                const int p = jb.pre_idx[k];
+                const S ps = (S)jb.pre_ps[k];
+                const abamd_row_meta_t pm = meta[p];
+                if (bj < pm.beg || bj > pm.end) continue;
+                const S *pH = arena + pm.off;
+                if ((S)(pH[bj - pm.beg] - e1 + ps) == Hj) {
+                    dev_push_cigar(jb.cigar, &wk.n_c, jb.cigar_cap, 2, 1, wk.id, bj - 1, &wk.status);
+                    wk.bi = p; wk.id = jb.row_node_id[p]; hit = 1;
+                    wk.look_end = 0;
+                    break;
                 }
             }
-            if (!hit) { /* deletion */
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj < pm.beg || bj > pm.end) continue;
-                    const S *pH = arena + pm.off;
-                    if ((S)(pH[bj - pm.beg] - e1 + ps) == Hj) {
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 2, 1, id, bj - 1, &status);
-                        bi = p; id = jb.row_node_id[bi]; hit = 1;
-                        if (look_end) look_end = 0;
-                        break;
-                    }
-                }
-            }
-            if (!hit) { /* insertion */
-                if ((S)(Hjm1 - e1) == Hj) {
-                    dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, 1, id, bj - 1, &status);
-                    --bj;
-                    if (look_end) look_end = 0;
-                    hit = 1; ++n_aln;
-                }
-            }
-            if (!hit) {
-                for (int k = pq0; k < pq1; ++k) {
-                    const int p = jb.pre_idx[k];
-                    const S ps = (S)jb.pre_ps[k];
-                    const abamd_row_meta_t pm = meta[p];
-                    if (bj - 1 < pm.beg || bj - 1 > pm.end) continue;
-                    const S *pH = arena + pm.off;
-                    if ((S)(pH[bj - 1 - pm.beg] + s + ps) == Hj) {
-                        dev_push_cigar(cig, &n_c, jb.cigar_cap, 0, 1, id, bj - 1, &status);
-                        bi = p; --bj; id = jb.row_node_id[bi]; hit = 1;
-                        ++n_aln; n_matched += is_match;
-                        look_end = 0;
-                        break;
-                    }
-                }
-            }
-            if (!hit) { status = ABAMD_JOB_BT_DEAD_END; break; }
         }
-        if (status == ABAMD_JOB_OK && bj > 0)
-            dev_push_cigar(cig, &n_c, jb.cigar_cap, 1, bj, -1, bj - 1, &status);
-        res->status = status;
-        res->n_cigar = n_c;
-        res->n_aln_bases = n_aln;
-        res->n_matched_bases = n_matched;
-        res->node_e = jb.row_node_id[best_i]; res->query_e = best_j - 1;
-        res->node_s = jb.row_node_id[start_i]; res->query_s = start_j - 1;
+        if (!hit && (S)(Hjm1 - e1) == Hj) { /* insertion */
+            dev_push_cigar(jb.cigar, &wk.n_c, jb.cigar_cap, 1, 1, wk.id, bj - 1, &wk.status);
+            --wk.bj;
+            wk.look_end = 0;
+            hit = 1; ++wk.n_aln;
+        }
+        if (!hit) {
+            hit = mw_walk_match<S>(jb, wk, 1, pq0, pq1, s, is_match, Hj);
+            if (hit) wk.look_end = 0;
+        }
+        if (!hit) { wk.status = ABAMD_JOB_BT_DEAD_END; break; }
     }
-}
-
-/* one-wave ag/lg kernels kept as an A/B fallback (ABPOA_AMD_SW_AGLG=1) */
-static int use_sw_aglg(void) {
-    static int v = -1;
-    if (v < 0) v = getenv("ABPOA_AMD_SW_AGLG") != nullptr;
-    return v;
+    mw_walk_end(jb, res, wk, best_i, best_j);
 }
 
 extern "C" void abamd_launch_ag_i16(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
                                     int n_jobs, void *stream) {
-    if (use_sw_aglg()) {
-        int blocks = (n_jobs + JOBS_PER_BLOCK - 1) / JOBS_PER_BLOCK;
-        hipLaunchKernelGGL((ag_global_kernel<int16_t>), dim3(blocks), dim3(WAVE * JOBS_PER_BLOCK), 0,
-                           (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
-        return;
-    }
     hipLaunchKernelGGL((ag_global_mw_kernel<int16_t>), dim3(n_jobs), dim3(MWT), 0,
                        (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
 }
 extern "C" void abamd_launch_ag_i32(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
                                     int n_jobs, void *stream) {
-    if (use_sw_aglg()) {
-        int blocks = (n_jobs + JOBS_PER_BLOCK - 1) / JOBS_PER_BLOCK;
-        hipLaunchKernelGGL((ag_global_kernel<int32_t>), dim3(blocks), dim3(WAVE * JOBS_PER_BLOCK), 0,
-                           (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
-        return;
-    }
     hipLaunchKernelGGL((ag_global_mw_kernel<int32_t>), dim3(n_jobs), dim3(MWT), 0,
                        (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
 }
 extern "C" void abamd_launch_lg_i16(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
                                     int n_jobs, void *stream) {
-    if (use_sw_aglg()) {
-        int blocks = (n_jobs + JOBS_PER_BLOCK - 1) / JOBS_PER_BLOCK;
-        hipLaunchKernelGGL((lg_global_kernel<int16_t>), dim3(blocks), dim3(WAVE * JOBS_PER_BLOCK), 0,
-                           (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
-        return;
-    }
     hipLaunchKernelGGL((lg_global_mw_kernel<int16_t>), dim3(n_jobs), dim3(MWT), 0,
                        (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
 }
 extern "C" void abamd_launch_lg_i32(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
                                     int n_jobs, void *stream) {
-    if (use_sw_aglg()) {
-        int blocks = (n_jobs + JOBS_PER_BLOCK - 1) / JOBS_PER_BLOCK;
-        hipLaunchKernelGGL((lg_global_kernel<int32_t>), dim3(blocks), dim3(WAVE * JOBS_PER_BLOCK), 0,
-                           (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
-        return;
-    }
     hipLaunchKernelGGL((lg_global_mw_kernel<int32_t>), dim3(n_jobs), dim3(MWT), 0,
                        (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
 }
