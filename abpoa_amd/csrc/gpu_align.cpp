@@ -643,8 +643,16 @@ static int batch_launch(GpuCtx &C, PendingBatch &PB) {
         {
             abamd_gpu_job_t *J = (abamd_gpu_job_t*)D.jobs.p;
             abamd_gpu_res_t *R = (abamd_gpu_res_t*)D.results.p;
-            if (abpt->gap_mode == ABPOA_CONVEX_GAP)
-                bits == 16 ? abamd_launch_cg_i16(J, R, n_jobs, D.stream) : abamd_launch_cg_i32(J, R, n_jobs, D.stream);
+            if (abpt->gap_mode == ABPOA_CONVEX_GAP) {
+                /* fast instantiation only if every job of the launch carries
+                 * the fields it hard-codes */
+                int fast = !abamd_dp_force_generic();
+                for (int i = 0; i < n_jobs && fast; ++i) {
+                    const abamd_gpu_job_t &jb = PB.hjobs[i];
+                    fast = abamd_cg_fast_eligible(jb.align_mode, jb.banded, jb.inc_path_score, jb.dp_ring);
+                }
+                bits == 16 ? abamd_launch_cg_i16(J, R, n_jobs, fast, D.stream) : abamd_launch_cg_i32(J, R, n_jobs, fast, D.stream);
+            }
             else if (abpt->gap_mode == ABPOA_AFFINE_GAP)
                 bits == 16 ? abamd_launch_ag_i16(J, R, n_jobs, D.stream) : abamd_launch_ag_i32(J, R, n_jobs, D.stream);
             else

@@ -297,6 +297,7 @@ struct Batch {
     int use_remain = 0, planes = 5;
     int serial_fold = 0;         /* ABPOA_AMD_SERIAL_FOLD: lane-0 mutation walk */
     int dp_ring = ABAMD_DP_RING_MAX; /* ABPOA_AMD_DP_RING: DP kernel LDS ring depth */
+    int dp_generic = 0;              /* ABPOA_AMD_DP_GENERIC: never the fast convex instantiation */
     double budget_bytes = 0;
     uint64_t retry_jobs = 0, pool_expands = 0;
     double t_host_build = 0, t_finish = 0;
@@ -466,8 +467,12 @@ void launch_slot(Batch &B, Slot &S) {
     {
         abamd_gpu_job_t *J = (abamd_gpu_job_t*)S.d_dpjobs.p;
         abamd_gpu_res_t *R = (abamd_gpu_res_t*)S.d_res.p;
-        if (abpt->gap_mode == ABPOA_CONVEX_GAP)
-            S.bits == 16 ? abamd_launch_cg_i16(J, R, n_jobs, S.stream) : abamd_launch_cg_i32(J, R, n_jobs, S.stream);
+        if (abpt->gap_mode == ABPOA_CONVEX_GAP) {
+            /* every job of a batch gets these fields from abpt and B (build_jobs) */
+            const int fast = !B.dp_generic &&
+                abamd_cg_fast_eligible(abpt->align_mode, abpt->wb >= 0, 0, B.dp_ring);
+            S.bits == 16 ? abamd_launch_cg_i16(J, R, n_jobs, fast, S.stream) : abamd_launch_cg_i32(J, R, n_jobs, fast, S.stream);
+        }
         else if (abpt->gap_mode == ABPOA_AFFINE_GAP)
             S.bits == 16 ? abamd_launch_ag_i16(J, R, n_jobs, S.stream) : abamd_launch_ag_i32(J, R, n_jobs, S.stream);
         else
@@ -1123,6 +1128,7 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     B.use_remain = (abpt->wb >= 0 || abpt->zdrop > 0);
     B.serial_fold = getenv("ABPOA_AMD_SERIAL_FOLD") ? 1 : 0;
     B.dp_ring = abamd_dp_ring_depth();
+    B.dp_generic = abamd_dp_force_generic();
     B.planes = abpt->gap_mode == ABPOA_CONVEX_GAP ? 3 /* F recomputed at backtrack */
              : abpt->gap_mode == ABPOA_AFFINE_GAP ? 3 : 1;
     B.sets.resize(n_sets);

@@ -83,6 +83,13 @@ typedef struct {
 #define ABAMD_DP_RING_MAX 10
 /* ABPOA_AMD_DP_RING, clamped to 1..ABAMD_DP_RING_MAX (unset: the maximum) */
 int abamd_dp_ring_depth(void);
+/* ABPOA_AMD_DP_GENERIC=1: never pick the convex kernel's fast instantiation
+ * (A/B runs and tests; same build) */
+int abamd_dp_force_generic(void);
+/* Whether a launch whose jobs all carry these fields may use the convex
+ * kernel's fast instantiation: global mode, banded, no path scores, ring at
+ * full depth. The caller also honours abamd_dp_force_generic(). */
+int abamd_cg_fast_eligible(int align_mode, int banded, int inc_path_score, int dp_ring);
 
 typedef struct {
     int32_t best_score;
@@ -95,10 +102,12 @@ typedef struct {
 } abamd_gpu_res_t;
 
 /* kernel launchers (gpu_kernels.hip); stream is a hipStream_t */
+/* the convex launchers take `fast` (abamd_cg_fast_eligible() of the jobs'
+ * fields): nonzero runs the fast instantiation */
 void abamd_launch_cg_i16(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
-                         int n_jobs, void *stream);
+                         int n_jobs, int fast, void *stream);
 void abamd_launch_cg_i32(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
-                         int n_jobs, void *stream);
+                         int n_jobs, int fast, void *stream);
 void abamd_launch_ag_i16(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
                          int n_jobs, void *stream);
 void abamd_launch_ag_i32(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,

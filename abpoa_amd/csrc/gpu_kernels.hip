@@ -25,8 +25,11 @@
  * Three kernels, each instantiated for int16 and for the int32 overflow
  * rescore, each serving global, local and extension mode: cg_global_mw_kernel
  * (convex gaps, the north-star path), ag_global_mw_kernel (affine) and
- * lg_global_mw_kernel (linear). The last two are the "multi-wave frame"
- * section plus their recurrence. The convex kernel keeps its own text (rolled
+ * lg_global_mw_kernel (linear). The convex kernel has a second template
+ * flag, FAST, for the north-star case (global, banded, no path scores, full
+ * ring depth): mode tests folded away, rolled row scalars as batched scalar
+ * loads; FAST = false serves everything else. The affine and linear kernels
+ * are the "multi-wave frame" section plus their recurrence. The convex kernel keeps its own text (rolled
  * predecessors, row ring, global-address-space pointers): calling the frame
  * for the three blocks it has in common measured 0.5 % lower at the bench
  * (DESIGN.md §6b); small source changes move these kernels' SGPR spills.
@@ -39,6 +42,7 @@
  * width (gpu_align.cpp, gpu_batch_resident.cpp).
  */
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "gpu_core.h"
 
 /* Compile-time phase profiler (make kprof): accumulates s_memtime cycles per
@@ -481,7 +485,14 @@ __device__ __forceinline__ void mw_walk_end(const abamd_gpu_job_t &jb, abamd_gpu
 /* one predecessor row as the gather sees it: slot >= 0 -> LDS ring */
 struct mw_pred_t { int slot, beg, end; };
 
-template <typename S>
+/* FAST is the north-star instantiation: global mode, banded, no path scores,
+ * ring at full depth. Those job fields are then compile-time constants, so
+ * the row loop carries none of the tests or of the state (running best,
+ * z-drop flag, ring depth, path-score switch) that serve the other modes.
+ * The host picks the instantiation per launch from the fields it writes into
+ * the jobs (abamd_cg_fast_eligible); FAST = false is the kernel for
+ * everything else. */
+template <typename S, bool FAST>
 __global__ __launch_bounds__(MWT, 4) /* 4 waves/SIMD: two blocks per CU */
 void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
                          abamd_gpu_res_t *__restrict__ results, int n_jobs) {
@@ -505,7 +516,9 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
     const S inf_min = (S)jb.inf_min;
     const S e1 = (S)jb.e1, e2 = (S)jb.e2;
     const S oe1 = (S)jb.oe1, oe2 = (S)jb.oe2;
-    const int local_mode = jb.align_mode == 1, extend_mode = jb.align_mode == 2;
+    const bool local_mode = !FAST && jb.align_mode == 1;
+    const bool extend_mode = !FAST && jb.align_mode == 2;
+    const bool banded = FAST || jb.banded;
     int32_t run_best = jb.inf_min;
     int run_best_i = 0, run_best_j = 0, run_best_remain = jb.max_remain[0];
     int zdropped = 0;
@@ -522,15 +535,24 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
     typedef __attribute__((address_space(1))) int gint_t;
     typedef __attribute__((address_space(1))) uint8_t gu8_t;
     typedef __attribute__((address_space(1))) abamd_row_meta_t gmeta_t;
+    /* FAST reads the row CSR and max_remain through constant-address-space
+     * pointers: an earlier kernel or copy wrote them and this kernel only
+     * reads them, so the scalar cache is coherent, and a load at a uniform
+     * index (every rolled one is) becomes a scalar load straight into SGPRs
+     * with scalar address arithmetic: no VALU address chain, no VGPR and no
+     * lane read per value. max_left, max_right and row_meta are written here
+     * and stay vector accesses. */
+    typedef __attribute__((address_space(4))) int cint_t;
+    typedef typename std::conditional<FAST, cint_t, gint_t>::type rint_t;
     GS *const g_arena = (GS*)jb.arena;
     const gu8_t *const g_query = (const gu8_t*)jb.query;
     const gu8_t *const g_row_base = (const gu8_t*)jb.row_base;
-    const gint_t *const g_pre_off = (const gint_t*)jb.pre_off;
-    const gint_t *const g_pre_idx = (const gint_t*)jb.pre_idx;
+    const rint_t *const g_pre_off = (const rint_t*)jb.pre_off;
+    const rint_t *const g_pre_idx = (const rint_t*)jb.pre_idx;
     const gint_t *const g_pre_ps = (const gint_t*)jb.pre_ps;
-    const gint_t *const g_out_off = (const gint_t*)jb.out_off;
-    const gint_t *const g_out_idx = (const gint_t*)jb.out_idx;
-    const gint_t *const g_max_remain = (const gint_t*)jb.max_remain;
+    const rint_t *const g_out_off = (const rint_t*)jb.out_off;
+    const rint_t *const g_out_idx = (const rint_t*)jb.out_idx;
+    const rint_t *const g_max_remain = (const rint_t*)jb.max_remain;
     gint_t *const g_max_left = (gint_t*)jb.max_left;
     gint_t *const g_max_right = (gint_t*)jb.max_right;
     gmeta_t *const g_meta = (gmeta_t*)jb.row_meta;
@@ -551,9 +573,10 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
     if (tid < MW_RING) ring_tbl[tid] = make_int4(-1, 0, -1, 0);
     __syncthreads();
 
-    const int depth = jb.dp_ring < 1 ? 1
+    const int depth = FAST ? ABAMD_DP_RING_MAX
+                    : jb.dp_ring < 1 ? 1
                     : (jb.dp_ring > ABAMD_DP_RING_MAX ? ABAMD_DP_RING_MAX : jb.dp_ring);
-    const int ips = jb.inc_path_score;
+    const int ips = FAST ? 0 : jb.inc_path_score;
     const int pre_last = g_pre_off[n_rows] - 1; /* clamps for the rolled loads */
     const int out_last = g_out_off[n_rows] - 1;
 
@@ -562,7 +585,7 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
     {
         int mr = g_max_remain[0] - end_remain - 1;
         int end0;
-        if (jb.banded) {
+        if (banded) {
             int t = g_max_right[0] > qlen - mr ? g_max_right[0] : qlen - mr;
             end0 = (qlen < t + w) ? qlen : t + w;
         } else end0 = qlen;
@@ -660,6 +683,13 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
                 k = cur_oo0 + i; if (k > out_last) k = out_last; if (k < 0) k = 0;
                 cur_oidx[i] = g_out_idx[k];
             }
+            /* FAST: all nine scalar loads in flight before the first wait:
+             * without this every result is moved to its spill lane at once,
+             * each behind a wait of its own */
+            if (FAST)
+                asm volatile("" :: "s"(cur_pk1), "s"(cur_oo1), "s"(cur_remain),
+                             "s"(cur_pidx[0]), "s"(cur_pidx[1]), "s"(cur_pidx[2]),
+                             "s"(cur_oidx[0]), "s"(cur_oidx[1]), "s"(cur_oidx[2]));
         }
         /* predecessor lookup: ring slot table first (one LDS read), else
          * row_meta. Uniform across the block; readfirstlane keeps the
@@ -726,7 +756,7 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
         int beg, end;
         {
             int mr = row_remain - end_remain - 1;
-            if (jb.banded) {
+            if (banded) {
                 int lo = ml_eff < qlen - mr ? ml_eff : qlen - mr;
                 beg = lo - w; if (beg < 0) beg = 0;
                 int hi = mr_eff > qlen - mr ? mr_eff : qlen - mr;
@@ -869,7 +899,7 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
              * (none of which reads this slot) has passed; B3 publishes it */
             if (!more && tid == 0)
                 ring_tbl[slot] = make_int4(cache_fits ? r : -1, beg, end, 0);
-            if (!more && (jb.banded || local_mode || extend_mode)) {
+            if (!more && (banded || local_mode || extend_mode)) {
                 /* last superchunk: fold the per-wave argmax publish into this
                  * barrier instead of paying a fourth barrier (and its store
                  * drain) after the loop */
@@ -898,7 +928,7 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
         }
         KPROF_T(mt3e);
 
-        if (jb.banded || local_mode || extend_mode) {
+        if (banded || local_mode || extend_mode) {
             /* per-wave argmax published under the loop's last barrier; every
              * thread repeats the 8-way combine from LDS (uniform result) */
             int mv = sc_red[0], ll = sc_red[MWAVES], rr = sc_red[2 * MWAVES];
@@ -924,7 +954,7 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
                 }
             }
             push_ml = 0x7fffffff; push_mr = -0x7fffffff;
-            if (!zdropped && jb.banded) {
+            if (!zdropped && banded) {
                 /* every thread performs the same idempotent update so its
                  * own later prefetch of row o is self-ordered */
                 auto push = [&](const int o) {
@@ -979,7 +1009,7 @@ void cg_global_mw_kernel(const abamd_gpu_job_t *__restrict__ jobs,
      * F-recompute below) ---- */
     int32_t best_score = run_best;
     int best_i = run_best_i, best_j = run_best_j;
-    if (jb.align_mode == 0) {
+    if (FAST || jb.align_mode == 0) {
         best_score = jb.inf_min; best_i = 0; best_j = 0;
         for (int k = jb.pre_off[n_rows - 1]; k < jb.pre_off[n_rows]; ++k) {
             const int p = jb.pre_idx[k];
@@ -1248,15 +1278,33 @@ extern "C" int abamd_dp_ring_depth(void) {
     return d;
 }
 
+extern "C" int abamd_dp_force_generic(void) {
+    /* read per call, like the ring depth */
+    const char *e = getenv("ABPOA_AMD_DP_GENERIC");
+    return e && *e && atoi(e) != 0;
+}
+
+extern "C" int abamd_cg_fast_eligible(int align_mode, int banded, int inc_path_score, int dp_ring) {
+    return align_mode == 0 && banded && !inc_path_score && dp_ring == ABAMD_DP_RING_MAX;
+}
+
 extern "C" void abamd_launch_cg_i16(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
-                                    int n_jobs, void *stream) {
-    hipLaunchKernelGGL((cg_global_mw_kernel<int16_t>), dim3(n_jobs), dim3(MWT), 0,
-                       (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
+                                    int n_jobs, int fast, void *stream) {
+    if (fast)
+        hipLaunchKernelGGL((cg_global_mw_kernel<int16_t, true>), dim3(n_jobs), dim3(MWT), 0,
+                           (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
+    else
+        hipLaunchKernelGGL((cg_global_mw_kernel<int16_t, false>), dim3(n_jobs), dim3(MWT), 0,
+                           (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
 }
 extern "C" void abamd_launch_cg_i32(const abamd_gpu_job_t *dev_jobs, abamd_gpu_res_t *dev_res,
-                                    int n_jobs, void *stream) {
-    hipLaunchKernelGGL((cg_global_mw_kernel<int32_t>), dim3(n_jobs), dim3(MWT), 0,
-                       (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
+                                    int n_jobs, int fast, void *stream) {
+    if (fast)
+        hipLaunchKernelGGL((cg_global_mw_kernel<int32_t, true>), dim3(n_jobs), dim3(MWT), 0,
+                           (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
+    else
+        hipLaunchKernelGGL((cg_global_mw_kernel<int32_t, false>), dim3(n_jobs), dim3(MWT), 0,
+                           (hipStream_t)stream, dev_jobs, dev_res, n_jobs);
 }
 
 /* ------------------------------------------------------------------ */
