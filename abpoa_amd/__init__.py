@@ -126,7 +126,7 @@ _ROW_TR = bytes(_ACGT.encode("ascii") + b"?" * (256 - len(_ACGT)))
 
 
 def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1,
-                      out_msa=False, out_cons=True):
+                      out_msa=False, out_cons=True, scoring=None):
     """Run the batched GPU driver over `sets` (list of list of bytes, codes
     0..3) and return, per set, the full callback payload as a dict:
       cons          list of consensus strings (one per cluster)
@@ -143,7 +143,9 @@ def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1,
                     (with out_cons) the consensus rows
     out_cons: with out_msa, whether the consensus rows are part of the MSA
     (the consensus itself is always delivered). Results without out_msa keep
-    exactly the keys listed first."""
+    exactly the keys listed first.
+    scoring: optional dict of integer scoring parameters to override, keys
+    among match, mismatch, gap_open1, gap_open2, gap_ext1, gap_ext2."""
     L = lib()
     L.abpoa_init_para.restype = ctypes.c_void_p
     L.abpoa_post_set_para.argtypes = [ctypes.c_void_p]
@@ -155,9 +157,13 @@ def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1,
         ctypes.POINTER(ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8))),
         CONS_CB, ctypes.c_void_p, ctypes.c_int]
     para = L.abpoa_init_para()
-    if cons_algrm is not None or max_n_cons != 1 or out_msa:
+    if cons_algrm is not None or max_n_cons != 1 or out_msa or scoring:
         from .pyabpoa import ParaT, ABPOA_HB, ABPOA_MF
         p = ctypes.cast(para, ctypes.POINTER(ParaT)).contents
+        for key, value in (scoring or {}).items():
+            if key not in ("match", "mismatch", "gap_open1", "gap_open2", "gap_ext1", "gap_ext2"):
+                raise ValueError("unknown scoring parameter %r" % key)
+            setattr(p, key, int(value))
         if cons_algrm is not None:
             p.cons_algrm = {"HB": ABPOA_HB, "MF": ABPOA_MF}[cons_algrm.upper()]
         if max_n_cons != 1:

@@ -381,6 +381,20 @@ extern "C" void abamd_pick_width(abpoa_para_t *abpt, int qlen, int gn, int *bits
     pick_width(abpt, qlen, gn, bits, inf_min);
 }
 
+/* int16 with a large gap extension lifts inf_min (INT16_MIN + penalties +
+ * 512 * ext_max) to zero or above: a "minus infinity" that beats real scores.
+ * The reference's own result there depends on its vector width (DESIGN
+ * section 6), so there is nothing to reproduce; refuse before any launch. The
+ * oracle refuses with the same words (oracle/ref_core.c). */
+extern "C" void abamd_refuse_positive_inf_min(int bits, int inf_min) {
+    if (bits != 16 || inf_min < 0) return;
+    fprintf(stderr, "[abpoa_amd] unsupported scoring: at int16 the out-of-band score floor is %d (>= 0) "
+                    "with these gap penalties; the reference's own result in this regime depends on its "
+                    "vector width. Use smaller gap extensions, or scores large enough to select int32.\n",
+            inf_min);
+    exit(EXIT_FAILURE);
+}
+
 /* Pipelined batch interface: begin() packs, uploads and launches without
  * waiting; finish() synchronizes and unpacks. The caller overlaps host-side
  * graph folds of one set group with the kernel of the other. begin/finish
@@ -491,6 +505,7 @@ static int prepare_internal(BatchJob *batch, int n_jobs, int slot, const int64_t
     }
     int bits_max = 16;
     for (int i = 0; i < n_jobs; ++i) if (bits_v[i] > bits_max) bits_max = bits_v[i];
+    for (int i = 0; i < n_jobs; ++i) abamd_refuse_positive_inf_min(bits_max, packs[i].jb.inf_min);
     g_pack_ns += now_ns() - t_pack0;
     uint64_t t_stage0 = now_ns();
 

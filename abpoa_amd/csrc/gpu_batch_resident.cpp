@@ -58,6 +58,7 @@ extern "C" {
 void abamd_stats_add_cells(uint64_t cells, uint64_t alg_bytes);
 void abamd_stats_add_kernel(uint64_t ns);
 void abamd_pick_width(abpoa_para_t *abpt, int qlen, int gn, int *bits, int *inf_min);
+void abamd_refuse_positive_inf_min(int bits, int inf_min);
 }
 
 namespace {
@@ -400,6 +401,7 @@ void build_jobs(Batch &B, Slot &S, const std::vector<int> &set_list, int r,
     }
     /* a mixed batch runs at the widest type; recompute inf_min at 32 bit */
     S.bits = bits_max;
+    for (int i = 0; i < n_jobs; ++i) abamd_refuse_positive_inf_min(bits_max, S.hjobs[i].inf_min);
     if (bits_max == 32) {
         for (int i = 0; i < n_jobs; ++i) {
             SetState &st = B.sets[set_list[i]];

@@ -988,6 +988,16 @@ int oracle_align_sequence_to_subgraph(abpoa_t *ab, abpoa_para_t *abpt,
         if (INT16_MIN + gap_oe1 > inf_min) inf_min = INT16_MIN + gap_oe1;
         if (INT16_MIN + gap_oe2 > inf_min) inf_min = INT16_MIN + gap_oe2;
         inf_min += 512 * (gap_ext1 > gap_ext2 ? gap_ext1 : gap_ext2);
+        if (inf_min >= 0) {
+            /* a "minus infinity" that beats real scores: the reference's own
+             * result here depends on its vector width; the
+             * GPU core refuses with the same words (gpu_align.cpp) */
+            fprintf(stderr, "[abpoa_amd] unsupported scoring: at int16 the out-of-band score floor is %d (>= 0) "
+                            "with these gap penalties; the reference's own result in this regime depends on its "
+                            "vector width. Use smaller gap extensions, or scores large enough to select int32.\n",
+                    inf_min);
+            exit(1);
+        }
         if (abpt->gap_mode == ABPOA_CONVEX_GAP)
             oracle_cg_i16(ab, abpt, beg_node_id, beg_index, end_node_id, end_index, index_map, query, qlen, inf_min, res);
         else if (abpt->gap_mode == ABPOA_AFFINE_GAP)

@@ -39,4 +39,19 @@ run expected_seq_fq.txt         seq.fa -r5          # FASTQ consensus
 run expected_test_cons.txt      test.fa
 run expected_3alleles_d3.txt    3alleles.fa -d3
 run expected_heter_cons.txt     heter.fa
+# flags that no GPU test ran before the seam harness: path scores, gap
+# placement, end bonus. Each is committed on an input on which the flag changes
+# this binary's output (tests/test_cpu_parity.py guards that), except -e, which
+# the reference parses and never reads: its golden equals expected_seq_extend.txt.
+run expected_seq_G_r1.txt       seq.fa -G -r1
+run expected_seq_R_r1.txt       seq.fa -R -r1
+run expected_seq_J_r1.txt       seq.fa -J -r1
+run expected_heter_R.txt        heter.fa -R
+run expected_seq_e5_extend.txt  seq.fa -e 5 -m2
+# affine -G changes nothing on the four inputs above; seed 1 is the first
+# 400 x 24 set at 13 % error on which it does (and linear -G as well)
+python3 ../make_synth.py synth13_seed1.fa --seed 1 --len 400 --depth 24 \
+    --sub 0.06 --del 0.04 --ins 0.03 2>/dev/null
+run expected_synth13_affine_G_r1.txt synth13_seed1.fa -O 4 -E 2 -G -r1
+run expected_synth13_linear_G_r1.txt synth13_seed1.fa -O 0 -E 2 -G -r1
 echo "golden fixtures regenerated"

@@ -117,3 +117,26 @@ def test_two_rank_one_gpu_smoke(tmp_path):
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
     assert out["n_gpus"] == 2 and out["value"] > 0
+
+
+REFUSED_SCORING = dict(match=90, mismatch=180, gap_open1=180, gap_open2=1080, gap_ext1=90, gap_ext2=45)
+
+
+@pytest.mark.parametrize("driver", ["resident", "host-fold"])
+def test_batch_drivers_refuse_positive_inf_min(driver):
+    """int16 scores with a gap extension that lifts inf_min to +14437 (DESIGN
+    section 6): both batch drivers refuse with the seam's one message before
+    any DP launch. The refusal ends the process, so it runs in a child."""
+    code = ("import sys; sys.path.insert(0, %r)\n"
+            "import numpy as np, abpoa_amd, bench\n"
+            "sets = bench.gen_sets(np.random.default_rng(5), 2, depth=4, qlen=200)\n"
+            "abpoa_amd.msa_batch_results(sets, n_threads=2, scoring=%r)\n"
+            "print('not refused')\n" % (ROOT, REFUSED_SCORING))
+    env = dict(os.environ)
+    env.pop("ABPOA_AMD_HOST_FOLD", None)
+    if driver == "host-fold":
+        env["ABPOA_AMD_HOST_FOLD"] = "1"
+    p = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode != 0 and b"not refused" not in p.stdout, p.stdout + p.stderr[-1000:]
+    assert b"unsupported scoring: at int16 the out-of-band score floor is 14437 (>= 0)" in p.stderr, p.stderr[-1000:]

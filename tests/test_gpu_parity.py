@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 from conftest import GOLDEN, ROOT, GPU_BIN, run_stdout
+import seam_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -196,3 +197,61 @@ def test_gpu_forced_int32_overflow(gpu_bin, cputest_bin, oracle_env, tmp_path):
         gpu = run_stdout([gpu_bin, str(fa)] + opts)
         cpu = run_stdout([cputest_bin, str(fa)] + opts, env=oracle_env)
         assert gpu == cpu, "int32-forced divergence opts=%r" % (opts,)
+
+
+# flags no GPU test ran before: the same goldens as tests/test_cpu_parity.py
+FLAG_GOLDENS = [
+    ("seq.fa", ["-G", "-r1"], "expected_seq_G_r1.txt"),
+    ("seq.fa", ["-R", "-r1"], "expected_seq_R_r1.txt"),
+    ("seq.fa", ["-J", "-r1"], "expected_seq_J_r1.txt"),
+    ("heter.fa", ["-R"], "expected_heter_R.txt"),
+    ("seq.fa", ["-e", "5", "-m2"], "expected_seq_e5_extend.txt"),
+    ("synth13_seed1.fa", ["-O", "4", "-E", "2", "-G", "-r1"], "expected_synth13_affine_G_r1.txt"),
+    ("synth13_seed1.fa", ["-O", "0", "-E", "2", "-G", "-r1"], "expected_synth13_linear_G_r1.txt"),
+]
+
+
+@pytest.mark.parametrize("fa,opts,expected", FLAG_GOLDENS,
+                         ids=["%s%s" % (c[0], "".join(c[1])) for c in FLAG_GOLDENS])
+def test_gpu_flag_goldens(gpu_bin, fa, opts, expected):
+    """-G, -R, -J and -e on the GPU against the reference's committed output."""
+    out = run_stdout([gpu_bin, os.path.join(GOLDEN, fa)] + opts)
+    assert out == open(os.path.join(GOLDEN, expected), "rb").read()
+
+
+@pytest.mark.parametrize("opts", [["-Q"], ["-Q", "-r1"], ["-Q", "-r5"]], ids=lambda o: "".join(o))
+def test_gpu_quality_weights_vs_oracle(gpu_bin, cputest_bin, oracle_env, tmp_path, opts):
+    """-Q on a FASTQ of 400 x 12: qualities weight the fold, and the next
+    read's DP runs on the graph that fold built."""
+    fq = sc.fastq(tmp_path / "q.fq")
+    cpu = run_stdout([cputest_bin, fq] + opts, env=oracle_env)
+    assert cpu and run_stdout([gpu_bin, fq] + opts) == cpu
+
+
+@pytest.mark.parametrize("opts", [[], ["-r1"]], ids=["cons", "rc-msa"])
+def test_gpu_incremental_restore_vs_oracle(gpu_bin, cputest_bin, oracle_env, tmp_path, opts):
+    """-i: restore the graph from a -r4 dump of the first 6 reads, then align
+    the other 18 into it on the GPU."""
+    dump, rest = sc.restore_inputs(
+        tmp_path, lambda first: run_stdout([cputest_bin, first, "-r4"], env=oracle_env))
+    cpu = run_stdout([cputest_bin, "-i", str(dump), str(rest)] + opts, env=oracle_env)
+    assert cpu and run_stdout([gpu_bin, "-i", str(dump), str(rest)] + opts) == cpu
+
+
+@pytest.mark.parametrize("opts", [["-s"], ["-s", "-r1"], ["-s", "-O", "4", "-E", "2", "-r1"]],
+                         ids=lambda o: "".join(o))
+def test_gpu_amb_strand_vs_oracle(gpu_bin, cputest_bin, oracle_env, tmp_path, opts):
+    """-s: every third read is reverse-complemented; best_score of the poor
+    forward alignment decides whether the other strand is tried and taken."""
+    fa = sc.every_third_reversed(sc.synth13(tmp_path / "s.fa"), tmp_path / "rc.fa")
+    cpu = run_stdout([cputest_bin, fa] + opts, env=oracle_env)
+    assert cpu and run_stdout([gpu_bin, fa] + opts) == cpu
+
+
+def test_gpu_positive_inf_min_is_refused(gpu_bin):
+    """int16 with a gap extension that lifts inf_min to +14437: refused with
+    the oracle's words before any kernel is launched."""
+    p = subprocess.run([gpu_bin, os.path.join(GOLDEN, "seq.fa"), "-M", "90", "-X", "180",
+                        "-O", "180,1080", "-E", "90,45"], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert p.returncode != 0 and p.stdout == b""
+    assert b"unsupported scoring: at int16 the out-of-band score floor is 14437 (>= 0)" in p.stderr
