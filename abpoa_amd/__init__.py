@@ -121,6 +121,33 @@ def reset_fold_stats():
     L.abpoa_amd_reset_fold_stats()
 
 
+_BATCH_KEYS = ("resident_calls", "hostfold_calls", "dp_retry_jobs", "dp_retry_launches",
+               "pool_expands", "big_chunks", "noop_folds", "seam_retry_jobs",
+               "launches_i16", "launches_i32")
+
+
+def get_batch_stats():
+    """Path counters of the batched drivers since the last reset, as a dict:
+    resident_calls / hostfold_calls (which driver served each msa_batch call),
+    dp_retry_jobs / dp_retry_launches (DP arena overflows of the resident
+    driver and the launches that redid them), pool_expands, big_chunks,
+    noop_folds (empty CIGAR on an existing graph), seam_retry_jobs (arena
+    overflows of the aligner seam), launches_i16 / launches_i32 (resident DP
+    launches by score width)."""
+    L = lib()
+    L.abpoa_amd_get_batch_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)] * len(_BATCH_KEYS)
+    L.abpoa_amd_get_batch_stats.restype = None
+    v = [ctypes.c_uint64() for _ in _BATCH_KEYS]
+    L.abpoa_amd_get_batch_stats(*[ctypes.byref(x) for x in v])
+    return dict(zip(_BATCH_KEYS, (x.value for x in v)))
+
+
+def reset_batch_stats():
+    L = lib()
+    L.abpoa_amd_reset_batch_stats.restype = None
+    L.abpoa_amd_reset_batch_stats()
+
+
 _ACGT = "ACGTN-"
 _ROW_TR = bytes(_ACGT.encode("ascii") + b"?" * (256 - len(_ACGT)))
 

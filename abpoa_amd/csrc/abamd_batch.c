@@ -127,6 +127,10 @@ int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, const int *n_se
                                  const int *const *seq_lens, const uint8_t *const *const *seqs,
                                  abpoa_amd_cons_cb cb, void *user, int n_host_threads);
 
+/* calls served by the resident [0] and the host-fold [1] driver
+ * (abpoa_amd_get_batch_stats) */
+uint64_t abamd_batch_calls[2];
+
 int abpoa_amd_msa_batch(abpoa_para_t *abpt, int n_sets, const int *n_seqs,
                         const int *const *seq_lens, const uint8_t *const *const *seqs,
                         abpoa_amd_cons_cb cb, void *user, int n_host_threads) {
@@ -138,10 +142,13 @@ int abpoa_amd_msa_batch(abpoa_para_t *abpt, int n_sets, const int *n_seqs,
         for (s = 0; s < n_sets && ok; ++s)
             for (i = 0; i < n_seqs[s]; ++i)
                 if (seq_lens[s][i] < 1) { ok = 0; break; }
-        if (ok)
+        if (ok) {
+            __atomic_fetch_add(&abamd_batch_calls[0], 1, __ATOMIC_RELAXED);
             return abpoa_amd_msa_batch_resident(abpt, n_sets, n_seqs, seq_lens, seqs,
                                                 cb, user, n_host_threads);
+        }
     }
+    __atomic_fetch_add(&abamd_batch_calls[1], 1, __ATOMIC_RELAXED);
     {
         /* fold thread-count override: at ~250 threads the concurrent folds'
          * ~10 MB graph working sets thrash the LLC (measured ~20x per-call

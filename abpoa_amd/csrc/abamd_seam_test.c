@@ -33,6 +33,11 @@
  *   --both-strands   also align the reverse complement of every read
  *   --batch          (GPU) afterwards one abamd_gpu_align_batch call with one
  *                    job per input file against that file's final graph
+ *   --cells          per whole-graph alignment one line "seam cells read R: rows N
+ *                    qlen Q oracle C est E n_cigar K": the oracle's banded cells per
+ *                    plane against the arena reservation of the product drivers,
+ *                    rows * (2w + 160) + qlen + 64 (job_est_cells in
+ *                    gpu_batch_resident.cpp, pack_job in gpu_align.cpp)
  *   --mutate F@R     (twin) F in best_score n_cigar node_s node_e query_s
  *                    query_e n_aln_bases n_matched_bases cigar_op cigar_node
  *                    cigar_query cigar_last, applied to read R's whole-graph
@@ -83,7 +88,8 @@ static long g_reads, g_alns, g_words, g_mismatches, g_longest_ins;
 static long g_n16, g_n32, g_fast, g_generic;
 #endif
 
-static int opt_settings, opt_windows, opt_both, opt_batch;
+static int opt_settings, opt_windows, opt_both, opt_batch, opt_cells;
+static void (*g_oracle_cells)(int64_t *cells, int64_t *rows);
 static char *mut_field; static int mut_read = -1, mut_applied;
 
 static const char *const SETTING_NAME[3] = { "default", "ABPOA_AMD_DP_GENERIC=1", "ABPOA_AMD_DP_RING=1" };
@@ -191,6 +197,13 @@ static abpoa_res_t align_pair(abpoa_t *ab, abpoa_para_t *abpt, int beg_id, int e
     abpoa_res_t ro; memset(&ro, 0, sizeof(ro));
     reset_band(ab, abpt);
     g_oracle(ab, abpt, beg_id, end_id, q, qlen, &ro);
+    if (opt_cells && whole) {
+        int64_t cells = 0, rows = 0;
+        g_oracle_cells(&cells, &rows);
+        int w = abpt->wb < 0 ? qlen : abpt->wb + (int)(abpt->wf * qlen);
+        printf("seam cells read %d: rows %lld qlen %d oracle %lld est %lld n_cigar %d\n", read_i, (long long)rows, qlen,
+               (long long)cells, (long long)(rows * (2 * (int64_t)w + 160) + qlen + 64), ro.n_cigar);
+    }
     int s, n_set = opt_settings ? 3 : 1;
     for (s = 0; s < n_set; ++s) {
         abpoa_res_t rd; memset(&rd, 0, sizeof(rd));
@@ -326,7 +339,8 @@ int main(int argc, char **argv) {
         { "settings", no_argument, 0, 1000 }, { "windows", required_argument, 0, 1001 },
         { "no-cigar", no_argument, 0, 1002 }, { "rev-cigar", no_argument, 0, 1003 },
         { "both-strands", no_argument, 0, 1004 }, { "batch", no_argument, 0, 1005 },
-        { "mutate", required_argument, 0, 1006 }, { 0, 0, 0, 0 } };
+        { "mutate", required_argument, 0, 1006 }, { "cells", no_argument, 0, 1007 },
+        { 0, 0, 0, 0 } };
     int c, i; char *s;
     abpoa_para_t *abpt = abpoa_init_para();
     while ((c = getopt_long(argc, argv, "m:M:X:O:E:b:f:z:e:GRJQct:", lopts, NULL)) >= 0) {
@@ -356,6 +370,7 @@ int main(int argc, char **argv) {
             case 1004: opt_both = 1; break;
             case 1005: opt_batch = 1; break;
             case 1006: mut_field = strdup(optarg); break;
+            case 1007: opt_cells = 1; break;
             default: return 2;
         }
     }
@@ -383,6 +398,11 @@ int main(int argc, char **argv) {
     if (!h) abamd_fatal("seam", "dlopen(%s) failed: %s", so, dlerror());
     g_oracle = (abpoa_amd_aligner_fn)(size_t)dlsym(h, "oracle_align_sequence_to_subgraph");
     if (!g_oracle) abamd_fatal("seam", "oracle_align_sequence_to_subgraph not found in %s", so);
+
+    if (opt_cells) {
+        g_oracle_cells = (void (*)(int64_t*, int64_t*))(size_t)dlsym(h, "oracle_last_cells");
+        if (!g_oracle_cells) abamd_fatal("seam", "oracle_last_cells not found in %s", so);
+    }
 
     int n_files = argc - optind;
     seam_file_t *files = (seam_file_t*)abamd_calloc((size_t)n_files, sizeof(seam_file_t));

@@ -50,6 +50,12 @@ extern "C" void abamd_timing_report(const char *tag) {
             (unsigned long long)g_launches.load(), (unsigned long long)g_retry_jobs.load());
 }
 
+/* seam arena-overflow retries, for abpoa_amd_get_batch_stats */
+extern "C" uint64_t abamd_seam_retry_jobs(int reset) {
+    if (reset) g_retry_jobs = 0;
+    return g_retry_jobs.load();
+}
+
 extern "C" void abpoa_amd_get_stats(uint64_t *dp_cells, uint64_t *kernel_ns, uint64_t *n_launches) {
     if (dp_cells) *dp_cells = g_dp_cells.load();
     if (kernel_ns) *kernel_ns = g_kernel_ns.load();

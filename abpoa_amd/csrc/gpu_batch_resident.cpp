@@ -59,6 +59,8 @@ void abamd_stats_add_cells(uint64_t cells, uint64_t alg_bytes);
 void abamd_stats_add_kernel(uint64_t ns);
 void abamd_pick_width(abpoa_para_t *abpt, int qlen, int gn, int *bits, int *inf_min);
 void abamd_refuse_positive_inf_min(int bits, int inf_min);
+uint64_t abamd_seam_retry_jobs(int reset);
+extern uint64_t abamd_batch_calls[2];
 }
 
 namespace {
@@ -74,6 +76,10 @@ std::atomic<uint64_t> g_msa_device_sets{0}, g_msa_host_sets{0}, g_msa_fallback_s
 /* graph-fold counters (abpoa_amd_get_fold_stats): which mutation walk each
  * settled fold job ran */
 std::atomic<uint64_t> g_fold_parallel{0}, g_fold_fallback{0}, g_fold_serial{0};
+
+/* path counters (abpoa_amd_get_batch_stats) */
+std::atomic<uint64_t> g_dp_retry_jobs{0}, g_dp_retry_launches{0}, g_pool_expands{0},
+                      g_big_chunks{0}, g_noop_folds{0}, g_launches_i16{0}, g_launches_i32{0};
 
 void count_fold_walk(int walk) {
     if (walk == ABAMD_FOLD_WALK_PARALLEL) g_fold_parallel += 1;
@@ -481,6 +487,7 @@ void launch_slot(Batch &B, Slot &S) {
             S.bits == 16 ? abamd_launch_lg_i16(J, R, n_jobs, S.stream) : abamd_launch_lg_i32(J, R, n_jobs, S.stream);
     }
     RHIP_CHECK(hipGetLastError());
+    (S.bits == 16 ? g_launches_i16 : g_launches_i32) += 1;
     RHIP_CHECK(hipEventRecord(S.ev1, S.stream));
     abamd_launch_fold_round((const abamd_fold_round_job_t*)S.d_fjobs.p, n_jobs, S.stream);
     RHIP_CHECK(hipGetLastError());
@@ -535,6 +542,7 @@ void expand_set(Batch &B, SetState &S, hipStream_t stream) {
     T.own_slab = slab;
     S = T;
     B.pool_expands += 1;
+    g_pool_expands += 1;
 }
 
 /* process the fold output for one job: update the host mirror, expanding and
@@ -555,7 +563,7 @@ void settle_fold(Batch &B, Slot &S, int i) {
             count_fold_walk(fo->walk);
             return;
         }
-        if (fo->status == ABAMD_FOLD_NOOP) return; /* graph + CSR unchanged */
+        if (fo->status == ABAMD_FOLD_NOOP) { g_noop_folds += 1; return; } /* graph + CSR unchanged */
         if (fo->status != ABAMD_FOLD_POOL_OVERFLOW) {
             fprintf(stderr, "[abpoa_amd] fold job %d unexpected status %d\n", i, fo->status);
             exit(EXIT_FAILURE);
@@ -605,6 +613,7 @@ void retry_failed(Batch &B, Slot &S) {
     }
     if (failed.empty()) return;
     B.retry_jobs += failed.size();
+    g_dp_retry_jobs += failed.size();
     Slot &R = g_ctx.slot[5];
     R.ensure_init();
     for (int attempt = 0;; ++attempt) {
@@ -614,6 +623,7 @@ void retry_failed(Batch &B, Slot &S) {
         }
         build_jobs(B, R, failed, S.round, floors.data());
         launch_slot(B, R);
+        g_dp_retry_launches += 1;
         RHIP_CHECK(hipStreamSynchronize(R.stream));
         {   /* kernel-time accounting for the retry launch */
             float dp_ms = 0.f, fold_ms = 0.f, t0 = 0.f, t2 = 0.f;
@@ -764,6 +774,14 @@ struct HostCons {
             if (k >= (int)c.cur->size()) break;
             const int s = (*c.cur)[k];
             abpoa_t *ab = abpoa_init();
+            if (c.hflat[s].node_n <= 2) {
+                /* a set with no reads has no graph: source and sink without an
+                 * edge, which abpoa_topological_sort refuses as "not a
+                 * connected DAG". Deliver the empty result of abpoa_init. */
+                ab->abs->n_seq = c.B.sets[s].n_seqs;
+                c.abs[s] = ab;
+                continue;
+            }
             c.slabs[s] = abamd_graph_from_flat(ab, &c.hflat[s], c.B.abpt, c.hflat[s].rid_n,
                                                c.hi2n[s], c.hn2i[s], c.hrem[s]);
             ab->abs->n_seq = c.B.sets[s].n_seqs;
@@ -791,7 +809,7 @@ struct HostCons {
 
     void release() {
         for (int s : done) {
-            abamd_graph_arena_release(abs[s], slabs[s]);
+            if (slabs[s]) abamd_graph_arena_release(abs[s], slabs[s]);
             abpoa_free(abs[s]);
             flat_graph_t &h = hflat[s];
             free(h.base); free(h.n_read); free(h.n_span_read);
@@ -1110,6 +1128,29 @@ extern "C" void abpoa_amd_reset_fold_stats(void) {
     g_fold_parallel = 0; g_fold_fallback = 0; g_fold_serial = 0;
 }
 
+extern "C" void abpoa_amd_get_batch_stats(uint64_t *resident_calls, uint64_t *hostfold_calls,
+        uint64_t *dp_retry_jobs, uint64_t *dp_retry_launches, uint64_t *pool_expands,
+        uint64_t *big_chunks, uint64_t *noop_folds, uint64_t *seam_retry_jobs,
+        uint64_t *launches_i16, uint64_t *launches_i32) {
+    if (resident_calls) *resident_calls = __atomic_load_n(&abamd_batch_calls[0], __ATOMIC_RELAXED);
+    if (hostfold_calls) *hostfold_calls = __atomic_load_n(&abamd_batch_calls[1], __ATOMIC_RELAXED);
+    if (dp_retry_jobs) *dp_retry_jobs = g_dp_retry_jobs.load();
+    if (dp_retry_launches) *dp_retry_launches = g_dp_retry_launches.load();
+    if (pool_expands) *pool_expands = g_pool_expands.load();
+    if (big_chunks) *big_chunks = g_big_chunks.load();
+    if (noop_folds) *noop_folds = g_noop_folds.load();
+    if (seam_retry_jobs) *seam_retry_jobs = abamd_seam_retry_jobs(0);
+    if (launches_i16) *launches_i16 = g_launches_i16.load();
+    if (launches_i32) *launches_i32 = g_launches_i32.load();
+}
+extern "C" void abpoa_amd_reset_batch_stats(void) {
+    __atomic_store_n(&abamd_batch_calls[0], 0, __ATOMIC_RELAXED);
+    __atomic_store_n(&abamd_batch_calls[1], 0, __ATOMIC_RELAXED);
+    g_dp_retry_jobs = 0; g_dp_retry_launches = 0; g_pool_expands = 0;
+    g_big_chunks = 0; g_noop_folds = 0; g_launches_i16 = 0; g_launches_i32 = 0;
+    (void)abamd_seam_retry_jobs(1);
+}
+
 extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, const int *n_seqs,
         const int *const *seq_lens, const uint8_t *const *const *seqs,
         abpoa_amd_cons_cb cb, void *user, int n_host_threads) {
@@ -1400,6 +1441,7 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
                 B.t_big_build += abamd_realtime() - tg;
                 B.t_big_gpu += tg - tb;
                 B.big_chunks += 1;
+                g_big_chunks += 1;
                 par ^= 1;
             }
             double tw = abamd_realtime();

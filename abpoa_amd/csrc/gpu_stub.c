@@ -66,6 +66,25 @@ void abpoa_amd_get_fold_stats(uint64_t *parallel_folds, uint64_t *fallback_folds
     if (serial_folds) *serial_folds = 0;
 }
 void abpoa_amd_reset_fold_stats(void) {}
+/* the call counters live in abamd_batch.c; nothing else exists here */
+extern uint64_t abamd_batch_calls[2];
+void abpoa_amd_get_batch_stats(uint64_t *resident_calls, uint64_t *hostfold_calls,
+                               uint64_t *dp_retry_jobs, uint64_t *dp_retry_launches,
+                               uint64_t *pool_expands, uint64_t *big_chunks,
+                               uint64_t *noop_folds, uint64_t *seam_retry_jobs,
+                               uint64_t *launches_i16, uint64_t *launches_i32) {
+    if (resident_calls) *resident_calls = abamd_batch_calls[0];
+    if (hostfold_calls) *hostfold_calls = abamd_batch_calls[1];
+    if (dp_retry_jobs) *dp_retry_jobs = 0;
+    if (dp_retry_launches) *dp_retry_launches = 0;
+    if (pool_expands) *pool_expands = 0;
+    if (big_chunks) *big_chunks = 0;
+    if (noop_folds) *noop_folds = 0;
+    if (seam_retry_jobs) *seam_retry_jobs = 0;
+    if (launches_i16) *launches_i16 = 0;
+    if (launches_i32) *launches_i32 = 0;
+}
+void abpoa_amd_reset_batch_stats(void) { abamd_batch_calls[0] = abamd_batch_calls[1] = 0; }
 void abamd_timing_report(const char *tag) { (void)tag; }
 
 static abamd_batch_job_t *stub_slot_batch[8];

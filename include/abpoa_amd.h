@@ -303,6 +303,31 @@ void abpoa_amd_get_fold_stats(uint64_t *parallel_folds, uint64_t *fallback_folds
                               uint64_t *serial_folds);
 void abpoa_amd_reset_fold_stats(void);
 
+/* Path counters of the batched drivers, for tests that must prove which
+ * recovery path a run took. All are cumulative since the last reset:
+ *   resident_calls     abpoa_amd_msa_batch calls served by the device-resident
+ *                      driver
+ *   hostfold_calls     calls served by the host-fold driver
+ *   dp_retry_jobs      DP jobs of the resident driver whose arena reservation
+ *                      overflowed and that were sent to the retry slot
+ *   dp_retry_launches  launches on the retry slot; more than one per group of
+ *                      failed jobs means a doubled reservation overflowed again
+ *   pool_expands       graph-pool expansions (a set's slab doubled)
+ *   big_chunks         chunks of items that exceeded the per-launch budget
+ *   noop_folds         fold jobs that found an empty CIGAR on an existing
+ *                      graph and left it untouched
+ *   seam_retry_jobs    arena-overflow retries of the aligner seam (sequential
+ *                      CLI and host-fold driver)
+ *   launches_i16/_i32  DP launches of the resident driver by score width
+ * Any pointer may be NULL. Builds without the GPU core count the calls and
+ * report zeros for the rest. */
+void abpoa_amd_get_batch_stats(uint64_t *resident_calls, uint64_t *hostfold_calls,
+                               uint64_t *dp_retry_jobs, uint64_t *dp_retry_launches,
+                               uint64_t *pool_expands, uint64_t *big_chunks,
+                               uint64_t *noop_folds, uint64_t *seam_retry_jobs,
+                               uint64_t *launches_i16, uint64_t *launches_i32);
+void abpoa_amd_reset_batch_stats(void);
+
 #ifdef __cplusplus
 }
 #endif

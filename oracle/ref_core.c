@@ -114,6 +114,15 @@ typedef struct {
 
 #define ROWP(T, bs, r, plane) ((T*)(bs)->arena + ((bs)->row_off[r] * (bs)->n_planes + (int64_t)(plane) * ((bs)->dp_end[r] - (bs)->dp_beg[r] + 1)))
 
+/* Cells per plane (bs.used) and rows of the last alignment, for the test
+ * that sizes inputs against the product's arena reservation
+ * (tests/test_arena_overflow_cpu.py via abpoa_amd_seamtwin) */
+static int64_t oracle_last_used, oracle_last_rows;
+void oracle_last_cells(int64_t *cells, int64_t *rows) {
+    if (cells) *cells = oracle_last_used;
+    if (rows) *rows = oracle_last_rows;
+}
+
 /* The DP proper, templated over score width via macro expansion. */
 #define DEFINE_ORACLE_CG(SCORE_T, SUFFIX)                                                                     \
 static int oracle_cg_##SUFFIX(abpoa_t *ab, abpoa_para_t *abpt, int beg_node_id, int beg_index,                \
@@ -449,6 +458,7 @@ static int oracle_cg_##SUFFIX(abpoa_t *ab, abpoa_para_t *abpt, int beg_node_id, 
     }                                                                                                         \
     for (i = 0; i < n_rows; ++i) free(pre_index[i]);                                                          \
     free(pre_index); free(pre_n);                                                                             \
+    oracle_last_used = bs.used; oracle_last_rows = n_rows;                                                    \
     free(bs.row_off); free(bs.dp_beg); free(bs.dp_end); free(bs.arena);                                       \
     return best_score;                                                                                        \
 }
@@ -725,6 +735,7 @@ static int oracle_ag_##SUFFIX(abpoa_t *ab, abpoa_para_t *abpt, int beg_node_id, 
     }                                                                                                         \
     for (i = 0; i < n_rows; ++i) free(pre_index[i]);                                                          \
     free(pre_index); free(pre_n);                                                                             \
+    oracle_last_used = bs.used; oracle_last_rows = n_rows;                                                    \
     free(bs.row_off); free(bs.dp_beg); free(bs.dp_end); free(bs.arena);                                       \
     return best_score;                                                                                        \
 }
@@ -952,6 +963,7 @@ static int oracle_lg_##SUFFIX(abpoa_t *ab, abpoa_para_t *abpt, int beg_node_id, 
     }                                                                                                         \
     for (i = 0; i < n_rows; ++i) free(pre_index[i]);                                                          \
     free(pre_index); free(pre_n);                                                                             \
+    oracle_last_used = bs.used; oracle_last_rows = n_rows;                                                    \
     free(bs.row_off); free(bs.dp_beg); free(bs.dp_end); free(bs.arena);                                       \
     return best_score;                                                                                        \
 }

@@ -88,10 +88,14 @@ def test_resident_pool_expansion():
     sets = bench.gen_sets(rng, 3, depth=20, qlen=500)
     os.environ["ABPOA_AMD_NODE_ALPHA"] = "0.02"
     try:
+        abpoa_amd.reset_batch_stats()
         tight = abpoa_amd.msa_batch_consensus(sets, n_threads=2)
+        assert abpoa_amd.get_batch_stats()["pool_expands"] > 0, "the knob forced no expansion"
     finally:
         os.environ.pop("ABPOA_AMD_NODE_ALPHA", None)
+    abpoa_amd.reset_batch_stats()
     roomy = abpoa_amd.msa_batch_consensus(sets, n_threads=2)
+    assert abpoa_amd.get_batch_stats()["pool_expands"] == 0
     assert tight == roomy, "pool-expansion path changed the consensus"
 
 

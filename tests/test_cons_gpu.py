@@ -104,10 +104,15 @@ def test_pool_expansion_device_path():
     kernel must work on the re-carved (expanded) slab."""
     rng = np.random.default_rng(77)
     sets = _bench().gen_sets(rng, 3, depth=20, qlen=500)
+    import abpoa_amd
+    abpoa_amd.reset_batch_stats()
     tight, st = _run(sets, env={"ABPOA_AMD_NODE_ALPHA": "0.02"})
+    assert abpoa_amd.get_batch_stats()["pool_expands"] > 0, "the knob forced no expansion"
+    abpoa_amd.reset_batch_stats()
     assert st["device_sets"] == 3 and st["fallback_sets"] == 0 and st["host_sets"] == 0, st
     roomy, sr = _run(sets)
     assert sr["device_sets"] == 3 and sr["host_sets"] == 0, sr
+    assert abpoa_amd.get_batch_stats()["pool_expands"] == 0
     _assert_same(tight, roomy, "pool-expansion vs roomy")
 
 
