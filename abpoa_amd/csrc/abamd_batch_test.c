@@ -15,6 +15,16 @@
  * cells and plane bytes of abpoa_amd_get_stats/_stats2, so a test can prove
  * which path of the driver its input took.
  *
+ * --fold-check (anywhere before the files; abpoa_amd_batchgpu only) installs
+ * a fold probe (abpoa_amd_batch_set_fold_probe) and checks what the production
+ * fold kernel wrote after EVERY fold of every set against a host twin advanced
+ * by the serial abamd_flat_* passes (abamd_fold_round_check.c): counters,
+ * pools, chains with heads and tails, read-id bitsets, topological order,
+ * max_remain and the seven DP-row CSR arrays. The first difference is named on
+ * stderr (set, read, field, index) and the exit status is 1 once the batch
+ * call has returned; a "[fold-check] ..." summary line goes to stderr either
+ * way (tests/test_fold_round_gpu.py).
+ *
  * Two programs are built from this file:
  *   abpoa_amd_batchtest  linked with gpu_stub.o: the host-fold driver, with
  *                        the alignments routed through the dispatch seam, where
@@ -32,6 +42,7 @@
 #include <string.h>
 #include "abpoa_amd.h"
 #include "abamd_util.h"
+#include "abamd_fold_round_check.h"
 
 /* forward-declared file-local seq API (abamd_seq.c) */
 typedef struct abamd_fx_t abamd_fx_t;
@@ -93,13 +104,26 @@ static void print_stats(void) {
             (unsigned long long)cells, (unsigned long long)alg_bytes);
 }
 
+static void fold_probe(const abpoa_amd_fold_probe_t *p, void *user) {
+    abamd_frc_check((abamd_frc_t*)user, p, stderr);
+}
+
 int main(int argc, char **argv) {
-    int stats = 0, rc;
+    int stats = 0, rc, fold_check = 0;
     abpoa_para_t *abpt = abpoa_init_para();
+    {   /* the one long option: take it out before getopt sees it */
+        int i, k = 1;
+        for (i = 1; i < argc; ++i) {
+            if (strcmp(argv[i], "--fold-check") == 0) fold_check = 1;
+            else argv[k++] = argv[i];
+        }
+        argc = k;
+        argv[argc] = NULL;
+    }
     rc = abamd_cli_parse_opts(argc, argv, abpt, NULL, &stats);
     if (rc < 0) return 0;
     if (rc > 0 || argc - optind < 1) {
-        fprintf(stderr, "usage: %s [CLI alignment options] [-r1|-r2] [-S] set1.fa [set2.fa ...]\n", argv[0]);
+        fprintf(stderr, "usage: %s [CLI alignment options] [-r1|-r2] [-S] [--fold-check] set1.fa [set2.fa ...]\n", argv[0]);
         return 2;
     }
     const int arg0 = optind, out_msa = abpt->out_msa, out_cons = abpt->out_cons;
@@ -129,13 +153,32 @@ int main(int argc, char **argv) {
     out_t out; out.n = n_sets; out.out_msa = out_msa; out.out_cons = out_cons;
     out.cons = (char**)abamd_calloc(n_sets, sizeof(char*));
     out.msa = (char**)abamd_calloc(n_sets, sizeof(char*));
+    abamd_frc_t *frc = NULL;
+    if (fold_check) {
+        frc = abamd_frc_new(abpt, n_sets, n_seqs, (const int *const *)lens,
+                            (const uint8_t *const *const *)seqs);
+        abpoa_amd_batch_set_fold_probe(fold_probe, frc);
+    }
     abpoa_amd_msa_batch(abpt, n_sets, n_seqs,
                         (const int *const *)lens,
                         (const uint8_t *const *const *)seqs, cb, &out, 4);
+    abpoa_amd_batch_set_fold_probe(NULL, NULL);
     for (int s = 0; s < n_sets; ++s) {
         printf(">set_%d\n%s\n", s, out.cons[s] ? out.cons[s] : "");
         if (out.msa[s]) fputs(out.msa[s], stdout);
     }
     if (stats) { fflush(stdout); print_stats(); }
+    if (frc) {
+        uint64_t b[2];
+        fflush(stdout);
+        abamd_frc_summary(frc, stderr);
+        abpoa_amd_get_batch_stats(&b[0], &b[1], NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL);
+        if (abamd_frc_failed(frc)) return 1;
+        if (b[0] == 0) {
+            /* the host-fold driver has no fold kernel: nothing was checked */
+            fprintf(stderr, "--fold-check: the device-resident driver did not serve this call\n");
+            return 3;
+        }
+    }
     return 0;
 }

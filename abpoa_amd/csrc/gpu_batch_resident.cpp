@@ -545,6 +545,88 @@ void expand_set(Batch &B, SetState &S, hipStream_t stream) {
     g_pool_expands += 1;
 }
 
+/* Fold probe (abpoa_amd_batch_set_fold_probe): a test's view of what the
+ * fold kernel left in a set's slab. Runs on the driver's thread once the
+ * job's stream is idle; the set's next launch is not enqueued before its slot
+ * is finished, so nothing writes the slab while it is read. */
+abpoa_amd_fold_probe_fn g_fold_probe = nullptr;
+void *g_fold_probe_user = nullptr;
+
+static_assert(ABPOA_AMD_FOLD_PROBE_OK == ABAMD_FOLD_OK && ABPOA_AMD_FOLD_PROBE_NOOP == ABAMD_FOLD_NOOP,
+              "public probe status codes mirror gpu_fold.h");
+
+struct ProbeBufs {
+    std::vector<uint64_t> store[29]; /* 8-byte aligned backing, one per array */
+    int used = 0;
+    const void *fetch(const void *dev, size_t bytes, hipStream_t stream) {
+        std::vector<uint64_t> &v = store[used++];
+        v.resize(bytes / 8 + 1);
+        if (bytes) RHIP_CHECK(hipMemcpyAsync(v.data(), dev, bytes, hipMemcpyDeviceToHost, stream));
+        return v.data();
+    }
+};
+thread_local ProbeBufs g_probe_bufs;
+
+/* st's host mirror already carries fo's counters (fold OK) or is unchanged
+ * (no-op). dev_cigar/n_cigar: the job's CIGAR buffer, reversed in place by
+ * the kernel into the order it consumed; null/0 for the chain build. */
+void fire_fold_probe(Batch &B, const SetState &st, int set_idx, int read_idx,
+                     const abamd_fold_out_t *fo, const uint64_t *dev_cigar, int n_cigar,
+                     hipStream_t stream) {
+    abpoa_amd_fold_probe_t p;
+    memset(&p, 0, sizeof(p));
+    p.set_idx = set_idx; p.read_idx = read_idx;
+    p.status = fo->status;
+    p.use_remain = B.use_remain;
+    p.node_cap = st.g.node_cap; p.edge_cap = st.g.edge_cap; p.aln_cap = st.g.aln_cap;
+    p.rid_n = st.g.rid_n;
+    p.out.status = fo->status;
+    p.out.node_n = fo->node_n; p.out.edge_n_in = fo->edge_n_in;
+    p.out.edge_n_out = fo->edge_n_out; p.out.aln_n = fo->aln_n;
+    if (fo->status != ABAMD_FOLD_OK) { g_fold_probe(&p, g_fold_probe_user); return; }
+    p.walk = fo->walk;
+    p.out.n_rows = fo->n_rows; p.out.n_pre = fo->n_pre; p.out.n_out = fo->n_out;
+    p.out.walk = fo->walk;
+    /* the counts size the downloads: refuse any that leave the slab */
+    if (fo->node_n < 2 || fo->node_n > st.g.node_cap || fo->edge_n_in < 0 ||
+        fo->edge_n_in > st.g.edge_cap || fo->edge_n_out < 0 || fo->edge_n_out > st.g.edge_cap ||
+        fo->aln_n < 0 || fo->aln_n > st.g.aln_cap || fo->n_rows < 0 || fo->n_rows > st.g.node_cap ||
+        fo->n_pre < 0 || fo->n_pre > st.g.edge_cap || fo->n_out < 0 || fo->n_out > st.g.edge_cap ||
+        n_cigar < 0) {
+        fprintf(stderr, "[abpoa_amd] fold probe: set %d read %d reports counts outside its pools "
+                        "(node_n %d edges %d/%d aln_n %d n_rows %d n_pre %d n_out %d)\n",
+                set_idx, read_idx, fo->node_n, fo->edge_n_in, fo->edge_n_out, fo->aln_n,
+                fo->n_rows, fo->n_pre, fo->n_out);
+        exit(EXIT_FAILURE);
+    }
+    ProbeBufs &pb = g_probe_bufs;
+    pb.used = 0;
+    const flat_graph_t &g = st.g;
+    const size_t nn = (size_t)fo->node_n, ei = (size_t)fo->edge_n_in, eo = (size_t)fo->edge_n_out,
+                 an = (size_t)fo->aln_n, nr = (size_t)fo->n_rows;
+    auto ints = [&](const int *dev, size_t n) { return (const int*)pb.fetch(dev, 4 * n, stream); };
+    p.n_cigar = n_cigar;
+    p.cigar = n_cigar ? (const uint64_t*)pb.fetch(dev_cigar, 8 * (size_t)n_cigar, stream) : nullptr;
+    p.base = (const uint8_t*)pb.fetch(g.base, nn, stream);
+    p.n_read = ints(g.n_read, nn); p.n_span_read = ints(g.n_span_read, nn);
+    p.in_head = ints(g.in_head, nn); p.in_tail = ints(g.in_tail, nn);
+    p.out_head = ints(g.out_head, nn); p.out_tail = ints(g.out_tail, nn);
+    p.aln_head = ints(g.aln_head, nn);
+    p.in_to = ints(g.in_to, ei); p.in_w = ints(g.in_w, ei); p.in_next = ints(g.in_next, ei);
+    p.out_to = ints(g.out_to, eo); p.out_w = ints(g.out_w, eo); p.out_next = ints(g.out_next, eo);
+    p.rid_pool = g.rid_n > 0 ? (const uint64_t*)pb.fetch(g.rid_pool, 8 * eo * (size_t)g.rid_n, stream)
+                             : nullptr;
+    p.aln_id = ints(g.aln_id, an); p.aln_next = ints(g.aln_next, an);
+    p.i2n = ints(st.i2n, nn); p.n2i = ints(st.n2i, nn); p.rem = ints(st.rem, nn);
+    p.row_base = (const uint8_t*)pb.fetch(st.row_base, nr, stream);
+    p.row_node_id = ints(st.row_node_id, nr);
+    p.pre_off = ints(st.pre_off, nr + 1); p.out_off = ints(st.out_off, nr + 1);
+    p.row_remain = ints(st.row_remain, nr);
+    p.pre_idx = ints(st.pre_idx, (size_t)fo->n_pre); p.out_idx = ints(st.out_idx, (size_t)fo->n_out);
+    RHIP_CHECK(hipStreamSynchronize(stream));
+    g_fold_probe(&p, g_fold_probe_user);
+}
+
 /* process the fold output for one job: update the host mirror, expanding and
  * relaunching on pool overflow until the fold lands */
 void settle_fold(Batch &B, Slot &S, int i) {
@@ -561,9 +643,16 @@ void settle_fold(Batch &B, Slot &S, int i) {
             st.n_pre = fo->n_pre;
             st.n_out = fo->n_out;
             count_fold_walk(fo->walk);
+            if (g_fold_probe)
+                fire_fold_probe(B, st, S.set_of[i], S.round, fo, S.hfjobs[i].cigar,
+                                ((const abamd_gpu_res_t*)S.h_read.p)[i].n_cigar, S.stream);
             return;
         }
-        if (fo->status == ABAMD_FOLD_NOOP) { g_noop_folds += 1; return; } /* graph + CSR unchanged */
+        if (fo->status == ABAMD_FOLD_NOOP) { /* graph + CSR unchanged */
+            g_noop_folds += 1;
+            if (g_fold_probe) fire_fold_probe(B, st, S.set_of[i], S.round, fo, nullptr, 0, S.stream);
+            return;
+        }
         if (fo->status != ABAMD_FOLD_POOL_OVERFLOW) {
             fprintf(stderr, "[abpoa_amd] fold job %d unexpected status %d\n", i, fo->status);
             exit(EXIT_FAILURE);
@@ -1143,6 +1232,11 @@ extern "C" void abpoa_amd_get_batch_stats(uint64_t *resident_calls, uint64_t *ho
     if (launches_i16) *launches_i16 = g_launches_i16.load();
     if (launches_i32) *launches_i32 = g_launches_i32.load();
 }
+extern "C" void abpoa_amd_batch_set_fold_probe(abpoa_amd_fold_probe_fn fn, void *user) {
+    g_fold_probe_user = user;
+    g_fold_probe = fn;
+}
+
 extern "C" void abpoa_amd_reset_batch_stats(void) {
     __atomic_store_n(&abamd_batch_calls[0], 0, __ATOMIC_RELAXED);
     __atomic_store_n(&abamd_batch_calls[1], 0, __ATOMIC_RELAXED);
@@ -1370,6 +1464,7 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
             st.n_pre = fo->n_pre;
             st.n_out = fo->n_out;
             count_fold_walk(fo->walk);
+            if (g_fold_probe) fire_fold_probe(B, st, all[i], 0, fo, nullptr, 0, S.stream);
         }
         S.active = false;
     }

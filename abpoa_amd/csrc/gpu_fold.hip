@@ -175,8 +175,9 @@ extern "C" void abamd_kprof_fold_reset(void) {
 /* produces; these versions compute the same values with all 64 lanes  */
 /* (per-node independence, wave prefix scans), cutting the per-set     */
 /* fold latency that otherwise matches the DP kernel's whole wall.     */
-/* Byte-parity with the host path is enforced end-to-end by            */
-/* tests/test_batch_gpu.py (resident vs host-fold vs sequential CLI).  */
+/* What each of these passes writes is compared with the serial twin   */
+/* after every fold, field by field, in the production slab layout:    */
+/* tests/test_fold_round_gpu.py (abpoa_amd_batchgpu --fold-check).     */
 /* ------------------------------------------------------------------ */
 
 #define FOLD_WAVE 64
@@ -233,12 +234,18 @@ __device__ static void dev_topo_bfs(const flat_graph_t *fg, int *index_to_node_i
 
 /* weight-descending adjacency sort — per-node work is independent, so nodes
  * stride across lanes. The host reference's pairwise-swap pass with strict <
- * (abamd_flat_sort_adjacency) is a STABLE selection sort: position j ends
- * with the first-occurring maximum of the remaining edges. Typical degrees
- * (<= 64: at most one edge per read plus merges) sort via a small private
- * array; larger degrees fall back to an in-place stable selection over the
- * chain — identical order, no O(KB) per-lane scratch (a 1024-int array here
- * forced a multi-GB device scratch pool that OOM'd full-HBM runs). */
+ * (abamd_flat_sort_adjacency) puts the first-occurring maximum of the
+ * remaining edges at position j, but it is NOT stable: the edge it displaces
+ * lands at the maximum's old place, behind its equals. The order of
+ * equal-weight edges decides DP and consensus ties, so both branches here
+ * perform exactly those swaps. Typical degrees (<= 64: at most one edge per
+ * read plus merges) sort via a small private array; larger degrees swap the
+ * chain's entries in place — identical order, no O(KB) per-lane scratch (a
+ * 1024-int array here forced a multi-GB device scratch pool that OOM'd
+ * full-HBM runs). An earlier big-degree branch was a stable selection and
+ * disagreed with the reference as soon as a node of degree > 64 had to
+ * reorder; tests/test_fold_round_gpu.py (the staircases) holds both to the
+ * twin now. */
 #define SORT_LOC 64
 __device__ static void dev_sort_chain(int *head, int *tail, int *next,
                                       const int *w) {
@@ -262,21 +269,30 @@ __device__ static void dev_sort_chain(int *head, int *tail, int *next,
         *tail = loc[n - 1];
         return;
     }
-    /* rare big-degree fallback: stable selection by chain re-linking */
-    int out_head = -1, out_tail = -1;
-    while (*head != -1) {
-        int best = *head, prev_best = -1, prev = *head;
-        for (e = next[*head]; e != -1; prev = e, e = next[e])
-            if (w[e] > w[best]) { best = e; prev_best = prev; }
-        if (prev_best == -1) *head = next[best];
-        else next[prev_best] = next[best];
-        if (out_tail == -1) out_head = best;
-        else next[out_tail] = best;
-        out_tail = best;
+    /* rare big-degree fallback: the same pairwise swaps on the chain itself.
+     * ej walks the positions j, ek the positions k > j; "swap" exchanges the
+     * two edges' places in the chain by re-linking. */
+    int prev_j = -1, ej = *head;
+    while (next[ej] != -1) {
+        int prev_k = ej, ek = next[ej];
+        while (ek != -1) {
+            if (w[ej] < w[ek]) {
+                const int nk = next[ek];
+                if (prev_k == ej) {          /* neighbours: j -> k -> X becomes k -> j -> X */
+                    next[ek] = ej;
+                } else {
+                    next[ek] = next[ej];
+                    next[prev_k] = ej;
+                }
+                next[ej] = nk;
+                if (prev_j == -1) *head = ek; else next[prev_j] = ek;
+                { const int t = ej; ej = ek; ek = t; }
+            }
+            prev_k = ek; ek = next[ek];
+        }
+        prev_j = ej; ej = next[ej];
     }
-    next[out_tail] = -1;
-    *head = out_head;
-    *tail = out_tail;
+    *tail = ej;
 }
 
 __device__ static void dev_par_sort_adjacency(flat_graph_t *fg, int lane) {

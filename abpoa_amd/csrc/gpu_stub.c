@@ -85,6 +85,8 @@ void abpoa_amd_get_batch_stats(uint64_t *resident_calls, uint64_t *hostfold_call
     if (launches_i32) *launches_i32 = 0;
 }
 void abpoa_amd_reset_batch_stats(void) { abamd_batch_calls[0] = abamd_batch_calls[1] = 0; }
+/* no device fold to look at */
+void abpoa_amd_batch_set_fold_probe(abpoa_amd_fold_probe_fn fn, void *user) { (void)fn; (void)user; }
 void abamd_timing_report(const char *tag) { (void)tag; }
 
 static abamd_batch_job_t *stub_slot_batch[8];

@@ -328,6 +328,64 @@ void abpoa_amd_get_batch_stats(uint64_t *resident_calls, uint64_t *hostfold_call
                                uint64_t *launches_i16, uint64_t *launches_i32);
 void abpoa_amd_reset_batch_stats(void);
 
+/* TEST HOOK: look at what the device-resident driver's fold kernel wrote,
+ * fold by fold. With a probe installed the driver calls it once for every
+ * fold job that settles — the first read's chain build, the folds of the
+ * pipelined rounds, folds carried by a DP retry launch and folds relaunched
+ * after a pool expansion alike — after synchronizing the job's stream and
+ * downloading the set's state into host buffers the driver owns. The pointers
+ * are valid only during the call. With no probe installed the cost is one
+ * pointer test per settled fold.
+ *
+ * status is ABPOA_AMD_FOLD_PROBE_OK, or ABPOA_AMD_FOLD_PROBE_NOOP for a job
+ * that found an empty CIGAR on an existing graph and left everything as it
+ * was: then `out` carries the graph's counters only and every array pointer
+ * and n_cigar is 0.
+ *
+ * Arrays hold their live counts: node arrays out.node_n entries, the in pools
+ * out.edge_n_in, the out pools out.edge_n_out (rid_pool rid_n words per
+ * out-edge, NULL when rid_n == 0), the aligned pool out.aln_n; i2n, n2i and
+ * rem out.node_n entries (rem is unspecified when !use_remain: the kernel does
+ * not write it); row_base, row_node_id and row_remain out.n_rows entries,
+ * pre_off and out_off out.n_rows + 1, pre_idx out.n_pre, out_idx out.n_out.
+ * cigar is the job's CIGAR in the forward order the fold consumed it; the
+ * first read's chain build has none (n_cigar 0, cigar NULL).
+ *
+ * Threading: the driver runs every launch and every settle on the thread
+ * that called abpoa_amd_msa_batch, so the probe is called on that thread,
+ * from inside that call, one fold at a time. Install or remove it only while
+ * no batch call is running. Builds without the GPU core accept and ignore
+ * it. */
+#define ABPOA_AMD_FOLD_PROBE_OK   0
+#define ABPOA_AMD_FOLD_PROBE_NOOP 3
+typedef struct {
+    int set_idx, read_idx;
+    int status;
+    int walk;                    /* 0 single-lane on request, 1 lane-parallel,
+                                    2 lane-parallel tripped a check, redone serially */
+    int use_remain;              /* the job's: band or z-drop in use */
+    int node_cap, edge_cap, aln_cap, rid_n;   /* the set's slab at this fold */
+    struct {                     /* the record the kernel wrote for the job */
+        int32_t status, node_n, edge_n_in, edge_n_out, aln_n, n_rows, n_pre, n_out, walk;
+    } out;
+    int n_cigar;
+    const uint64_t *cigar;
+    /* flat graph */
+    const uint8_t *base;
+    const int *n_read, *n_span_read;
+    const int *in_head, *in_tail, *out_head, *out_tail, *aln_head;
+    const int *in_to, *in_w, *in_next, *out_to, *out_w, *out_next;
+    const uint64_t *rid_pool;
+    const int *aln_id, *aln_next;
+    /* derived: topological order and its inverse, max_remain */
+    const int *i2n, *n2i, *rem;
+    /* the next round's DP-row CSR */
+    const uint8_t *row_base;
+    const int *row_node_id, *pre_off, *out_off, *row_remain, *pre_idx, *out_idx;
+} abpoa_amd_fold_probe_t;
+typedef void (*abpoa_amd_fold_probe_fn)(const abpoa_amd_fold_probe_t *p, void *user);
+void abpoa_amd_batch_set_fold_probe(abpoa_amd_fold_probe_fn fn, void *user);
+
 #ifdef __cplusplus
 }
 #endif

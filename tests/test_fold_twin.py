@@ -41,6 +41,21 @@ def test_twin_synthetic(tmp_path):
         _run(fa, ["-r1"])
 
 
+def test_twin_fold_round_inputs(tmp_path):
+    """The inputs of tests/test_fold_round_gpu.py that no other case here
+    covers: there the flat twin is the reference the production fold kernel is
+    held to, so here the twin itself is held to the pointer graph on them —
+    the staircases (one node's degree past 64, two read-id words) and the
+    150-base bubble. The amino set is not here: abpoa_amd_foldtwin takes no
+    -c / matrix options, so it cannot build an m = 27 graph; the pointer-graph
+    side of that set is covered by the batch harness against the oracle
+    (tests/test_resident_paths_gpu.py, amino workload)."""
+    import fold_cases as fc
+    for fa in (fc.prefix_staircase(tmp_path), fc.suffix_staircase(tmp_path), fc.bubble(tmp_path)):
+        _run(fa)
+        _run(fa, ["-r1"])
+
+
 @pytest.mark.gpu
 def test_device_fold_kernel(tmp_path):
     """abamd_fold_kernel on a real GPU: one launch per read mutates the
