@@ -100,6 +100,32 @@ def reset_msa_stats():
     L.abpoa_amd_reset_msa_stats()
 
 
+_MULTICONS_KEYS = ("device_sets", "host_sets", "fallback_sets", "one_cluster_sets",
+                   "clusters", "cand_cols", "d2h_bytes", "kernel_ns")
+
+
+def get_multicons_stats():
+    """Multi-consensus counters of the batched driver since the last reset, for
+    calls with max_n_cons > 1 made under ABPOA_AMD_DEVICE_MULTICONS only:
+    dict(device_sets, host_sets, fallback_sets, one_cluster_sets, clusters,
+    cand_cols, d2h_bytes, kernel_ns). device_sets had their candidate columns
+    found, and their per-cluster consensus computed, on the GPU; host_sets
+    downloaded their graph (fallback_sets of them after a non-OK device
+    status); one_cluster_sets / clusters / cand_cols describe the device sets."""
+    L = lib()
+    L.abpoa_amd_get_multicons_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)] * len(_MULTICONS_KEYS)
+    L.abpoa_amd_get_multicons_stats.restype = None
+    v = [ctypes.c_uint64() for _ in _MULTICONS_KEYS]
+    L.abpoa_amd_get_multicons_stats(*[ctypes.byref(x) for x in v])
+    return dict(zip(_MULTICONS_KEYS, (x.value for x in v)))
+
+
+def reset_multicons_stats():
+    L = lib()
+    L.abpoa_amd_reset_multicons_stats.restype = None
+    L.abpoa_amd_reset_multicons_stats()
+
+
 def get_fold_stats():
     """Graph-fold counters of the batched driver since the last reset:
     dict(parallel_folds, fallback_folds, serial_folds). parallel_folds ran the
@@ -163,7 +189,7 @@ def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1,
       n_seq         reads in the set
     cons_algrm: None = library default (HB), "MF" = most-frequent (exercises
     the per-edge read-id bitsets on the device-resident path).
-    max_n_cons: 1 or 2 consensus sequences per set.
+    max_n_cons: 1, 2 or 3 consensus sequences per set.
     out_msa: also build the row-column MSA; each result then additionally holds
       msa_len       number of columns
       msa           list of row strings over "ACGTN-": the read rows, then
@@ -194,8 +220,8 @@ def msa_batch_results(sets, n_threads=4, cons_algrm=None, max_n_cons=1,
         if cons_algrm is not None:
             p.cons_algrm = {"HB": ABPOA_HB, "MF": ABPOA_MF}[cons_algrm.upper()]
         if max_n_cons != 1:
-            if max_n_cons < 1 or max_n_cons > 2:
-                raise ValueError("max_n_cons must be 1 or 2")
+            if max_n_cons < 1 or max_n_cons > 3:
+                raise ValueError("max_n_cons must be 1, 2 or 3")
             p.max_n_cons = max_n_cons
         if out_msa:
             # before abpoa_post_set_para, which switches read-id tracking on

@@ -234,14 +234,22 @@ static int collect_2medoids(const het_pos_t *hp, int het_i, int **dm, int *med) 
     return 0;
 }
 
-/* partition index of a read over het columns 0..het_i (:893-902) */
-static int partition_index(const het_pos_t *hp, int het_i, int read_i) {
-    int k, idx = 0;
-    for (k = 0; k <= het_i; ++k) {
-        idx *= hp[k].n_uniq_alles + 1;
-        idx += hp[k].read_id_to_allele_idx[read_i] + 1;
-    }
-    return idx;
+/* two reads share a partition when they carry the same allele (or none) at
+ * every het column 0..het_i. The reference numbers the partitions in base
+ * n_uniq_alles + 1 (:893-902) and counts them in an array of that many
+ * entries; past ~20 columns that product overflows an int (undefined there).
+ * Comparing the allele vectors gives the same answers wherever the numbering
+ * is injective, and has no such limit. */
+/* how often the clustering took the two paths where the reference's behaviour
+ * is undefined: [0] collect_1medoid over more than 20 het columns, [1] fewer
+ * seeds than clusters asked for. Tests read them through the twin. */
+uint64_t abamd_clu_path_counts[2];
+
+static int same_partition(const het_pos_t *hp, int het_i, int read_a, int read_b) {
+    int k;
+    for (k = 0; k <= het_i; ++k)
+        if (hp[k].read_id_to_allele_idx[read_a] != hp[k].read_id_to_allele_idx[read_b]) return 0;
+    return 1;
 }
 
 /* add one medoid: prefer a read from a partition no medoid occupies (most
@@ -249,19 +257,16 @@ static int partition_index(const het_pos_t *hp, int het_i, int read_i) {
  * max-min-distance read among the top column's allele clusters (:904-971) */
 static int collect_1medoid(const het_pos_t *hp, int het_i, int **dm, int n_seq,
                            int *med, int n_medoids) {
-    int n_partitions = 1, k, i, j;
-    for (k = 0; k <= het_i; ++k) n_partitions *= hp[k].n_uniq_alles + 1;
-    int *pcount = (int*)abamd_calloc(n_partitions, sizeof(int));
-    for (i = 0; i < n_seq; ++i) pcount[partition_index(hp, het_i, i)] += 1;
+    int i, j;
     int max_dis = 0, max_read_i = -1, max_ptotal = -1;
+    if (het_i >= 20) __atomic_fetch_add(&abamd_clu_path_counts[0], 1, __ATOMIC_RELAXED);
     for (i = 0; i < n_seq; ++i) {
         int found = 0;
-        int pi = partition_index(hp, het_i, i);
-        int ptotal = pcount[pi];
         for (j = 0; j < n_medoids; ++j)
-            if (pi == partition_index(hp, het_i, med[j])) { found = 1; break; }
+            if (same_partition(hp, het_i, i, med[j])) { found = 1; break; }
         if (!found) {
-            int min_dis = INT_MAX;
+            int min_dis = INT_MAX, ptotal = 0;
+            for (j = 0; j < n_seq; ++j) ptotal += same_partition(hp, het_i, i, j);
             for (j = 0; j < n_medoids; ++j)
                 if (dm[i][med[j]] < min_dis) min_dis = dm[i][med[j]];
             if (ptotal > max_ptotal || (ptotal == max_ptotal && min_dis > max_dis)) {
@@ -284,7 +289,6 @@ static int collect_1medoid(const het_pos_t *hp, int het_i, int **dm, int n_seq,
             }
         }
     }
-    free(pcount);
     if (max_read_i != -1) { med[n_medoids] = max_read_i; return 1; }
     return 0;
 }
@@ -378,7 +382,17 @@ static int clu_reads_kmedoids(const het_pos_t *hp, const int *prio, int n_het, i
     for (i = 0; i < max_n_cons; ++i) clu_reads[i] = (int*)abamd_malloc((size_t)n_seq * sizeof(int));
     int to_collect = max_n_cons, n_clusters = 1;
     while (1) {
-        if (init_kmedoids(hp, prio, n_het, dm, n_seq, to_collect, med) <= 0) break;
+        int n_med = init_kmedoids(hp, prio, n_het, dm, n_seq, to_collect, med);
+        if (n_med <= 0) break;
+        if (n_med < to_collect) {
+            /* fewer seeds than clusters asked for: med[n_med..] was never
+             * written, and the reference goes on to read it as read ids
+             * (undefined there; a wild index here). No k-clustering can be
+             * seeded, so k shrinks as it does when a cluster stays too small. */
+            __atomic_fetch_add(&abamd_clu_path_counts[1], 1, __ATOMIC_RELAXED);
+            if (--to_collect < 2) break;
+            continue;
+        }
         int iter = 0;
         while (1) {
             int changed = kmedoids_update(dm, n_seq, to_collect, &med, clu_reads, n_clu_seqs);
@@ -409,16 +423,28 @@ static int clu_reads_kmedoids(const het_pos_t *hp, const int *prio, int n_het, i
     return n_clusters;
 }
 
-/* MSA -> het positions -> distances -> k-medoids clusters
- * (abpoa_multip_read_clu_kmedoids, :1136-1182) */
-static int multip_read_clu(abpoa_graph_t *g, abpoa_para_t *abpt, int n_seq,
-                           uint64_t ***clu_read_ids) {
-    int i, j, n_clu;
-    uint8_t **msa = (uint8_t**)abamd_malloc((size_t)n_seq * sizeof(uint8_t*));
-    int msa_l = collect_msa_matrix(g, abpt, msa, n_seq);
+/* The depth window of a candidate het column, as collect_cand_het_pos derives
+ * it from multip_read_clu's min_w: at least two symbols of a column must have
+ * min_het <= depth <= min_hom. The device het scan (abamd_msa_core.inc) gets
+ * the two bounds from here, so no floating point runs on the device. */
+void abamd_het_depth_bounds(int n_seq, const abpoa_para_t *abpt, int *min_het, int *min_hom) {
     int min_w = AB_MAX2(2, (int)ceil(n_seq * abpt->min_freq));
-    het_pos_t *hp = (het_pos_t*)abamd_malloc((size_t)msa_l * sizeof(het_pos_t));
-    int *prio = (int*)abamd_malloc((size_t)msa_l * sizeof(int));
+    *min_het = AB_MAX2(2, min_w / 2);
+    *min_hom = n_seq - *min_het;
+}
+
+/* het positions -> distances -> k-medoids clusters over an n_seq x msa_l
+ * matrix (gap code = m): everything of multip_read_clu after the matrix.
+ * The matrix may hold only the candidate het columns in their order (the
+ * device-resident driver downloads just those): collect_cand_het_pos leaves
+ * any other column at `if (n_uniq < 2) continue` before touching state, and
+ * a kept column's index is used only to address the matrix. */
+int abamd_read_clu_from_msa(uint8_t **msa, int msa_l, int n_seq, abpoa_para_t *abpt,
+                            uint64_t ***clu_read_ids) {
+    int i, j, n_clu;
+    int min_w = AB_MAX2(2, (int)ceil(n_seq * abpt->min_freq));
+    het_pos_t *hp = (het_pos_t*)abamd_malloc((size_t)(msa_l > 0 ? msa_l : 1) * sizeof(het_pos_t));
+    int *prio = (int*)abamd_malloc((size_t)(msa_l > 0 ? msa_l : 1) * sizeof(int));
     int n_het = collect_cand_het_pos(msa, msa_l, n_seq, abpt->m, min_w, hp, prio);
     if (n_het < 1) n_clu = 1;
     else {
@@ -433,6 +459,17 @@ static int multip_read_clu(abpoa_graph_t *g, abpoa_para_t *abpt, int n_seq,
         free(hp[i].clu_read_ids); free(hp[i].n_clu_reads); free(hp[i].read_id_to_allele_idx);
     }
     free(hp); free(prio);
+    return n_clu;
+}
+
+/* MSA -> het positions -> distances -> k-medoids clusters
+ * (abpoa_multip_read_clu_kmedoids, :1136-1182) */
+static int multip_read_clu(abpoa_graph_t *g, abpoa_para_t *abpt, int n_seq,
+                           uint64_t ***clu_read_ids) {
+    int i;
+    uint8_t **msa = (uint8_t**)abamd_malloc((size_t)n_seq * sizeof(uint8_t*));
+    int msa_l = collect_msa_matrix(g, abpt, msa, n_seq);
+    int n_clu = abamd_read_clu_from_msa(msa, msa_l, n_seq, abpt, clu_read_ids);
     for (i = 0; i < n_seq; ++i) free(msa[i]);
     free(msa);
     return n_clu;
@@ -611,6 +648,36 @@ void abamd_cons_from_path(abpoa_cons_t *abc, int n_seq, int cons_len, const int 
     }
     abc->cons_len[0] = cons_len;
     free(phred_of);
+}
+
+/* The same for n_clu >= 2 clusters (the device multi-consensus stage): masks
+ * holds n_clu * rid_n words, cluster c's read-id bitset at masks + c * rid_n,
+ * rid_n = (n_seq - 1) / 64 + 1; clu_n_seq / clu_read_ids come from the masks
+ * as heaviest_bundling fills them, phred from cons_phred_score(cov,
+ * clu_n_seq[c]). ids/bases/cov[c] hold cons_len[c] entries. `abc` must be
+ * cleared. */
+void abamd_cons_from_paths(abpoa_cons_t *abc, int n_seq, int n_clu, const uint64_t *masks,
+                           const int *cons_len, const int *const *ids,
+                           const uint8_t *const *bases, const int *const *cov) {
+    int c, i, j, r, max_len = 1;
+    const int rid_n = (n_seq - 1) / 64 + 1;
+    for (c = 0; c < n_clu; ++c) if (cons_len[c] > max_len) max_len = cons_len[c];
+    allocate_cons(abc, max_len, n_seq, n_clu);
+    for (c = 0; c < n_clu; ++c) {
+        const uint64_t *mask = masks + (size_t)c * rid_n;
+        int cnt = 0;
+        for (i = 0; i < rid_n; ++i) cnt += ab_amd_popcnt64(mask[i]);
+        abc->clu_n_seq[c] = cnt;
+        for (r = 0, cnt = 0; r < n_seq; ++r)
+            if (mask[r / 64] & (1ull << (r & 0x3f))) abc->clu_read_ids[c][cnt++] = r;
+        for (j = 0; j < cons_len[c]; ++j) {
+            abc->cons_node_ids[c][j] = ids[c][j];
+            abc->cons_base[c][j] = bases[c][j];
+            abc->cons_cov[c][j] = cov[c][j];
+            abc->cons_phred_score[c][j] = cons_phred_score(cov[c][j], abc->clu_n_seq[c]);
+        }
+        abc->cons_len[c] = cons_len[c];
+    }
 }
 
 /* Attach a downloaded row-major matrix as the msa_base rows

@@ -117,7 +117,9 @@ ABAMD_FC_FN int abamd_flat_hb_consensus(const flat_graph_t *fg, int n_seq,
  *         (r, sink_row], chain longer than the pool). Only a corrupt graph
  *         produces the latter; the path walk reports it.
  * Every successor row is checked to be > r, so rows on any path strictly
- * increase and all later loops are bounded by construction. */
+ * increase and all later loops are bounded by construction.
+ * (abamd_flat_cons_edge_scan_clu below is the same scan with cluster-filtered
+ * weights; keep the two in step.) */
 ABAMD_FC_FN void abamd_flat_cons_edge_scan(const flat_graph_t *fg, const int *i2n,
                                            const int *n2i, int sink_row,
                                            int *max_w, int *best, int lane, int n_lanes) {
@@ -157,7 +159,9 @@ ABAMD_FC_FN static int flat_cons_score_at(const int *score, const int *win, int 
  * st_w/st_b hold phase 1's results for the chunk; on return win[] holds the
  * chunk's scores and st_b[] the FINAL choices (successor row, or -1).
  * The tied/SRC re-scan is heaviest_bundling's decision logic verbatim, in
- * row space (chains were validated by phase 1, the graph is read-only). */
+ * row space (chains were validated by phase 1, the graph is read-only).
+ * abamd_flat_cons_sweep_chunk_clu below restates both rules with
+ * cluster-filtered weights: a change to either rule belongs in both. */
 ABAMD_FC_FN void abamd_flat_cons_sweep_chunk(const flat_graph_t *fg, const int *i2n,
                                              const int *n2i, int base, int sink_row,
                                              const int *score, const int *st_w,
@@ -278,6 +282,172 @@ ABAMD_FC_FN int abamd_flat_cons_phased(const flat_graph_t *fg, const int *i2n, c
     len = stage[1];
     if (status != ABAMD_CONS_OK) return status;
     abamd_flat_cons_gather(fg, i2n, path, len, cons_id, cons_base, cons_cov, lane, n_lanes);
+    *cons_len_out = len;
+    return ABAMD_CONS_OK;
+}
+
+/* ------------------------------------------------------------------ */
+/* Cluster-filtered variant (multi-consensus, n_clu >= 2).             */
+/* ------------------------------------------------------------------ */
+
+/* One heaviest-bundle pass of heaviest_bundling() for cluster `mask`
+ * (rid_n words): the four phases above with two differences. An edge's
+ * weight is the number of the cluster's reads on it (inclu_edge_weight
+ * without use_qv), popcount(rid_pool[e] & mask) summed over the words, in
+ * the phase-1 scan and in both re-scan rules; zero-weight ties are the
+ * normal case at nodes only another cluster's reads visit, so far more rows
+ * take the re-scan than with stored weights. And the gathered coverage is the
+ * sum of those counts over the node's out-edges: the reference's
+ * abpoa_node_cov, whose in-side term is always 0 (node_cov_clu,
+ * abamd_cons.c). The text is kept apart from the single-cluster functions so
+ * that their code, and abamd_cons_kernel's registers, stay as they are. */
+ABAMD_FC_FN static int flat_cons_w_clu(const flat_graph_t *fg, const uint64_t *mask, int e) {
+    int w, n = 0;
+    for (w = 0; w < fg->rid_n; ++w)
+        n += __builtin_popcountll(fg->rid_pool[(size_t)e * fg->rid_n + w] & mask[w]);
+    return n;
+}
+
+/* Phase 1, as abamd_flat_cons_edge_scan (same encoding of best[], same chain
+ * checks) */
+ABAMD_FC_FN void abamd_flat_cons_edge_scan_clu(const flat_graph_t *fg, const uint64_t *mask,
+                                               const int *i2n, const int *n2i, int sink_row,
+                                               int *max_w, int *best, int lane, int n_lanes) {
+    int r;
+    for (r = lane; r <= sink_row; r += n_lanes) {
+        const int id = i2n[r];
+        int w_max = INT32_MIN, b = -1, n_max = 0, ok = 1, steps = 0, e;
+        if ((unsigned)id >= (unsigned)fg->node_n || id == 1 /* SINK */) ok = 0;
+        else
+            for (e = fg->out_head[id]; e != -1; e = fg->out_next[e]) {
+                int to, row, w;
+                if ((unsigned)e >= (unsigned)fg->edge_n_out || ++steps > fg->edge_n_out) { ok = 0; break; }
+                to = fg->out_to[e];
+                if ((unsigned)to >= (unsigned)fg->node_n) { ok = 0; break; }
+                row = n2i[to];
+                if (row <= r || row > sink_row) { ok = 0; break; }
+                w = flat_cons_w_clu(fg, mask, e);
+                if (w > w_max) { w_max = w; b = row; n_max = 1; }
+                else if (w == w_max) { b = row; ++n_max; }
+            }
+        if (!ok || b < 0) { max_w[r] = 0; best[r] = -1; }
+        else {
+            max_w[r] = w_max;
+            best[r] = (n_max > 1 || id == 0 /* SRC */) ? ~b : b;
+        }
+    }
+}
+
+/* Phase 2, one staged chunk, as abamd_flat_cons_sweep_chunk */
+ABAMD_FC_FN void abamd_flat_cons_sweep_chunk_clu(const flat_graph_t *fg, const uint64_t *mask,
+                                                 const int *i2n, const int *n2i, int base,
+                                                 int sink_row, const int *score, const int *st_w,
+                                                 int *st_b, int *win) {
+    int l = sink_row - base, e;
+    if (l > ABAMD_CONS_CHUNK - 1) l = ABAMD_CONS_CHUNK - 1;
+    for (; l >= 0; --l) {
+        const int b = st_b[l];
+        if (b >= 0) {
+            win[l] = st_w[l] + flat_cons_score_at(score, win, base, b);
+        } else if (b == -1) {
+            win[l] = 0; /* SINK (score 0) or an unusable row */
+        } else {
+            const int id = i2n[base + l];
+            if (id == 0 /* SRC */) {
+                int max_row = -1, path_score = -1, path_max_w = -1;
+                for (e = fg->out_head[id]; e != -1; e = fg->out_next[e]) {
+                    const int row = n2i[fg->out_to[e]], w = flat_cons_w_clu(fg, mask, e);
+                    const int sc = flat_cons_score_at(score, win, base, row);
+                    if (w > path_max_w || (w == path_max_w && sc > path_score)) {
+                        max_row = row; path_score = sc; path_max_w = w;
+                    }
+                }
+                st_b[l] = max_row;
+                win[l] = 0;
+            } else {
+                int max_row = -1, mw = INT32_MIN;
+                for (e = fg->out_head[id]; e != -1; e = fg->out_next[e]) {
+                    const int row = n2i[fg->out_to[e]], w = flat_cons_w_clu(fg, mask, e);
+                    if (mw < w) { mw = w; max_row = row; }
+                    else if (mw == w && flat_cons_score_at(score, win, base, max_row) <=
+                                        flat_cons_score_at(score, win, base, row)) max_row = row;
+                }
+                st_b[l] = max_row;
+                win[l] = mw + flat_cons_score_at(score, win, base, max_row);
+            }
+        }
+    }
+}
+
+/* Phase 2, as abamd_flat_cons_sweep */
+ABAMD_FC_FN void abamd_flat_cons_sweep_clu(const flat_graph_t *fg, const uint64_t *mask,
+                                           const int *i2n, const int *n2i, int sink_row,
+                                           const int *max_w, int *best, int *score,
+                                           int *stage, int lane, int n_lanes) {
+    int *st_w = stage, *st_b = stage + ABAMD_CONS_CHUNK, *win = stage + 2 * ABAMD_CONS_CHUNK;
+    int base, l;
+    for (base = (sink_row / ABAMD_CONS_CHUNK) * ABAMD_CONS_CHUNK; base >= 0; base -= ABAMD_CONS_CHUNK) {
+        for (l = lane; l < ABAMD_CONS_CHUNK; l += n_lanes)
+            if (base + l <= sink_row) { st_w[l] = max_w[base + l]; st_b[l] = best[base + l]; }
+        ABAMD_FC_BARRIER();
+        if (lane == 0)
+            abamd_flat_cons_sweep_chunk_clu(fg, mask, i2n, n2i, base, sink_row, score, st_w, st_b, win);
+        ABAMD_FC_BARRIER();
+        for (l = lane; l < ABAMD_CONS_CHUNK; l += n_lanes)
+            if (base + l <= sink_row) { score[base + l] = win[l]; best[base + l] = st_b[l]; }
+        ABAMD_FC_BARRIER();
+    }
+}
+
+/* Phase 4: ids and bases as abamd_flat_cons_gather; coverage = the cluster's
+ * reads over the node's out-edges. Every path row passed phase 1's chain
+ * checks (a row that failed them has best = -1, which ends the walk), and the
+ * walk here is bounded again all the same. */
+ABAMD_FC_FN void abamd_flat_cons_gather_clu(const flat_graph_t *fg, const uint64_t *mask,
+                                            const int *i2n, const int *path, int cons_len,
+                                            int *cons_id, uint8_t *cons_base, int *cons_cov,
+                                            int lane, int n_lanes) {
+    int j;
+    for (j = lane; j < cons_len; j += n_lanes) {
+        const int id = i2n[path[j]];
+        int cov = 0, steps = 0, e;
+        for (e = fg->out_head[id]; e != -1; e = fg->out_next[e]) {
+            if ((unsigned)e >= (unsigned)fg->edge_n_out || ++steps > fg->edge_n_out) break;
+            cov += flat_cons_w_clu(fg, mask, e);
+        }
+        cons_id[j] = id;
+        cons_base[j] = fg->base[id];
+        cons_cov[j] = cov;
+    }
+}
+
+/* The four phases for one cluster; arguments as abamd_flat_cons_phased plus
+ * the cluster's mask of fg->rid_n words (only read). */
+ABAMD_FC_FN int abamd_flat_cons_phased_clu(const flat_graph_t *fg, const uint64_t *mask,
+                                           const int *i2n, const int *n2i,
+                                           int *max_w, int *best, int *score, int *path,
+                                           int *cons_id, uint8_t *cons_base, int *cons_cov,
+                                           int *stage, int *cons_len_out, int lane, int n_lanes) {
+    int sink_row, status, len;
+    *cons_len_out = 0;
+    if (fg->node_n <= 2 || fg->rid_n <= 0 || fg->edge_n_out < 0) return ABAMD_CONS_BAD_GRAPH;
+    sink_row = n2i[1 /* SINK */];
+    if (sink_row <= 0 || sink_row >= fg->node_n || n2i[0 /* SRC */] != 0 ||
+        i2n[0] != 0 || i2n[sink_row] != 1)
+        return ABAMD_CONS_BAD_GRAPH;
+    abamd_flat_cons_edge_scan_clu(fg, mask, i2n, n2i, sink_row, max_w, best, lane, n_lanes);
+    ABAMD_FC_BARRIER();
+    abamd_flat_cons_sweep_clu(fg, mask, i2n, n2i, sink_row, max_w, best, score, stage, lane, n_lanes);
+    if (lane == 0) {
+        int wl = 0;
+        stage[0] = abamd_flat_cons_walk(best, sink_row, path, &wl);
+        stage[1] = wl;
+    }
+    ABAMD_FC_BARRIER();
+    status = stage[0];
+    len = stage[1];
+    if (status != ABAMD_CONS_OK) return status;
+    abamd_flat_cons_gather_clu(fg, mask, i2n, path, len, cons_id, cons_base, cons_cov, lane, n_lanes);
     *cons_len_out = len;
     return ABAMD_CONS_OK;
 }

@@ -39,6 +39,12 @@ enum {
                                     outside the matrix: only a corrupt graph */
 };
 
+/* het scan (abamd_msa_core.inc): largest alphabet whose m + 1 depth counters
+ * it keeps in scalars, and the ints of its shared staging area (status word,
+ * spare, one flag per lane of a 64-lane group) */
+#define ABAMD_HET_MAX_M 5
+#define ABAMD_HET_STAGE (2 + 64)
+
 /* lane-parallel mutation walk (abamd_fold_par.inc): scratch and per-call
  * state. The six arrays hold `cap` ints each, `part` holds part_cap >=
  * ABAMD_PAR_PARTS * n_lanes ints; none of them overlaps another or the graph. */
@@ -142,7 +148,44 @@ int abamd_flat_msa_place(const flat_graph_t *fg, const int *col, int n_seq,
                          const uint8_t *cons_base, int cons_len,
                          int *stage, int lane, int n_lanes);
 
+/* one heaviest-bundle pass with cluster-filtered edge weights (multi-consensus,
+ * n_clu >= 2): abamd_flat_cons_phased plus the cluster's read-id mask of
+ * fg->rid_n words; coverage is the cluster's reads over the node's out-edges */
+int abamd_flat_cons_phased_clu(const flat_graph_t *fg, const uint64_t *mask,
+                               const int *i2n, const int *n2i,
+                               int *max_w, int *best, int *score, int *path,
+                               int *cons_id, uint8_t *cons_base, int *cons_cov,
+                               int *stage, int *cons_len_out, int lane, int n_lanes);
+
+/* one consensus row of the row-column MSA as a stage of its own: `row` holds
+ * msa_len bytes pre-filled with the gap code; stage 2 ints */
+int abamd_flat_msa_place_cons_row(int node_n, const int *col, int msa_len, uint8_t *row,
+                                  const int *cons_id, const uint8_t *cons_base, int cons_len,
+                                  int *stage, int lane, int n_lanes);
+
+/* het scan over the read rows (abamd_msa_core.inc). Count: the candidate
+ * columns' indices, ascending, into cand[cand_cap]; stage ABAMD_HET_STAGE
+ * ints. Gather: those columns as a row-major n_seq x n_cand matrix; stage 2
+ * ints. Both return ABAMD_MSA_*. */
+int abamd_flat_het_count(const uint8_t *msa, int n_seq, int msa_len, int m,
+                         int min_het, int min_hom, int *cand, int cand_cap,
+                         int *stage, int *n_cand_out, int lane, int n_lanes);
+int abamd_flat_het_gather(const uint8_t *msa, int n_seq, int msa_len, const int *cand,
+                          int n_cand, uint8_t *out, int *stage, int lane, int n_lanes);
+
 #ifdef ABPOA_AMD_H
+/* the depth window of a candidate het column for n_seq reads (abamd_cons.c) */
+void abamd_het_depth_bounds(int n_seq, const abpoa_para_t *abpt, int *min_het, int *min_hom);
+/* read clustering from an n_seq x msa_l matrix that holds all columns or the
+ * candidate het columns only (abamd_cons.c): returns n_clu; for n_clu >= 2
+ * *clu_read_ids gets n_clu separately allocated bitsets of (n_seq-1)/64+1 words */
+int abamd_read_clu_from_msa(uint8_t **msa, int msa_l, int n_seq, abpoa_para_t *abpt,
+                            uint64_t ***clu_read_ids);
+/* the n_clu >= 2 result from per-cluster consensus paths (abamd_cons.c);
+ * masks holds n_clu * ((n_seq-1)/64+1) words. `abc` must be cleared. */
+void abamd_cons_from_paths(abpoa_cons_t *abc, int n_seq, int n_clu, const uint64_t *masks,
+                           const int *cons_len, const int *const *ids,
+                           const uint8_t *const *bases, const int *const *cov);
 /* Build the single-cluster abpoa_cons_t the heaviest-bundle pass produces
  * from a consensus path (abamd_cons.c): phred from coverage on the host,
  * n_cons = 1, every read in cluster 0. `abc` must be cleared. */

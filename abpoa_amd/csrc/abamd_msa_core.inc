@@ -22,6 +22,13 @@
  * (abamd_fold_core.c) runs the very same code with one lane and is proven
  * against abpoa_generate_rc_msa by tests/test_msa_twin.
  *
+ * The device multi-consensus stage builds on the same read rows: one consensus
+ * row as a stage of its own (abamd_flat_msa_place_cons_row), and the het scan
+ * (abamd_flat_het_count, abamd_flat_het_gather) that finds the candidate
+ * heterozygous columns the host clustering needs; gpu_fold.hip wraps them in
+ * abamd_cons_row_kernel, abamd_het_count_kernel and abamd_het_gather_kernel,
+ * and tests/test_multicons_twin proves them with one lane.
+ *
  * Unlike abamd_flat_msa_rank (abamd_fold_core.inc, kept for the fold twin),
  * nothing here aborts: every index read from the graph is range-checked,
  * every chain walk and the stack are bounded, and a graph that fails a check
@@ -165,6 +172,46 @@ ABAMD_FC_FN int abamd_flat_msa_rank_cols(const flat_graph_t *fg, int *rank, int 
     return ABAMD_MSA_OK;
 }
 
+/* One consensus row, parallel over its positions: cons_base[i] goes to the
+ * column of cons_id[i] in `row` (msa_len bytes, pre-filled with the gap
+ * code). An id outside [2, node_n) or a column outside the row sets stage[0]
+ * instead of storing. The caller owns stage[0]'s initial value and the
+ * barriers around it. */
+ABAMD_FC_FN void abamd_flat_msa_cons_row(int node_n, const int *col, int msa_len, uint8_t *row,
+                                         const int *cons_id, const uint8_t *cons_base,
+                                         int cons_len, int *stage, int lane, int n_lanes) {
+    int i;
+    for (i = lane; i < cons_len; i += n_lanes) {
+        const int id = cons_id[i];
+        int c;
+        if (id < 2 || id >= node_n) { stage[0] = ABAMD_MSA_BAD_GRAPH; continue; }
+        c = col[id];
+        if ((unsigned)c >= (unsigned)msa_len) { stage[0] = ABAMD_MSA_BAD_GRAPH; continue; }
+        row[c] = cons_base[i];
+    }
+}
+
+/* The same as a stage of its own (the multi-consensus path places cluster
+ * c's row once that cluster's consensus exists). All lanes return the same
+ * status. stage: 2 ints shared by the group. */
+ABAMD_FC_FN int abamd_flat_msa_place_cons_row(int node_n, const int *col, int msa_len,
+                                              uint8_t *row, const int *cons_id,
+                                              const uint8_t *cons_base, int cons_len,
+                                              int *stage, int lane, int n_lanes) {
+    int status;
+    if (lane == 0) stage[0] = ABAMD_MSA_OK;
+    ABAMD_FC_BARRIER();
+    if (node_n <= 2 || msa_len <= 0 || cons_len < 0 || cons_len > node_n) {
+        if (lane == 0) stage[0] = ABAMD_MSA_BAD_GRAPH;
+    } else {
+        abamd_flat_msa_cons_row(node_n, col, msa_len, row, cons_id, cons_base, cons_len,
+                                stage, lane, n_lanes);
+    }
+    ABAMD_FC_BARRIER();
+    status = stage[0];
+    return status;
+}
+
 /* Stage 2 — placement into msa[rows x msa_len] (row-major, pre-filled with
  * the gap code), rows = n_seq read rows plus one consensus row when
  * cons_len >= 0 (pass cons_len < 0 for no consensus row).
@@ -209,13 +256,105 @@ ABAMD_FC_FN int abamd_flat_msa_place(const flat_graph_t *fg, const int *col, int
             }
             if (!ok) stage[0] = ABAMD_MSA_BAD_GRAPH;
         }
-        for (i = lane; i < cons_len; i += n_lanes) {
-            const int id = cons_id[i];
-            int c;
-            if (id < 2 || id >= fg->node_n) { stage[0] = ABAMD_MSA_BAD_GRAPH; continue; }
-            c = col[id];
+        abamd_flat_msa_cons_row(fg->node_n, col, msa_len, msa + (size_t)n_seq * msa_len,
+                                cons_id, cons_base, cons_len, stage, lane, n_lanes);
+    }
+    ABAMD_FC_BARRIER();
+    status = stage[0];
+    return status;
+}
+
+/* ------------------------------------------------------------------ */
+/* Het scan: the candidate heterozygous columns of the read rows.      */
+/* ------------------------------------------------------------------ */
+
+/* Launch 1 — which columns collect_cand_het_pos (abamd_cons.c) would look
+ * at: a column is a candidate when at least two of the m + 1 symbols (gap
+ * code = m) have min_het <= depth <= min_hom over the n_seq rows. The host
+ * derives the two bounds (abamd_het_depth_bounds), so this is integer work
+ * only. The multi-consensus stage downloads just these columns; every other
+ * column leaves the host clustering before it touches any state.
+ *
+ * Columns are taken n_lanes at a time, lane l counting column base + l, so a
+ * row's byte loads are adjacent across the group; with m <= ABAMD_HET_MAX_M
+ * the counters are six scalars. The candidates' column indices go to cand[]
+ * in ascending order: per chunk each lane publishes its flag in stage[2 +
+ * lane], sums the flags of the lanes before it (its slot) and of all lanes
+ * (the running base every lane keeps). A symbol above m, or a candidate past
+ * cand_cap, flags the job; nothing is stored out of bounds.
+ * stage: ABAMD_HET_STAGE ints shared by the group (n_lanes <= 64). All lanes
+ * return the same status and see the same *n_cand_out. */
+#define ABAMD_HET_IN(d) ((d) >= min_het && (d) <= min_hom)
+ABAMD_FC_FN int abamd_flat_het_count(const uint8_t *msa, int n_seq, int msa_len, int m,
+                                     int min_het, int min_hom, int *cand, int cand_cap,
+                                     int *stage, int *n_cand_out, int lane, int n_lanes) {
+    int base, total = 0, status;
+    *n_cand_out = 0;
+    if (lane == 0) stage[0] = ABAMD_MSA_OK;
+    ABAMD_FC_BARRIER();
+    if (n_seq <= 0 || msa_len <= 0 || m < 1 || m > ABAMD_HET_MAX_M || cand_cap < 0 ||
+        n_lanes > ABAMD_HET_STAGE - 2) {
+        if (lane == 0) stage[0] = ABAMD_MSA_BAD_GRAPH;
+    } else {
+        for (base = 0; base < msa_len; base += n_lanes) {
+            const int c = base + lane;
+            int flag = 0, before = 0, all = 0, l;
+            if (c < msa_len) {
+                int d0 = 0, d1 = 0, d2 = 0, d3 = 0, d4 = 0, d5 = 0, r, ok = 1;
+                for (r = 0; r < n_seq; ++r) {
+                    const int b = msa[(size_t)r * msa_len + c];
+                    d0 += b == 0; d1 += b == 1; d2 += b == 2;
+                    d3 += b == 3; d4 += b == 4; d5 += b == 5;
+                    if (b > m) ok = 0;
+                }
+                if (!ok) stage[0] = ABAMD_MSA_BAD_GRAPH;
+                /* a counter above m stays 0 on a sound matrix, below min_het >= 2 */
+                flag = ok && ABAMD_HET_IN(d0) + ABAMD_HET_IN(d1) + ABAMD_HET_IN(d2) +
+                             ABAMD_HET_IN(d3) + ABAMD_HET_IN(d4) + ABAMD_HET_IN(d5) >= 2;
+            }
+            stage[2 + lane] = flag;
+            ABAMD_FC_BARRIER();
+            for (l = 0; l < n_lanes; ++l) {
+                const int f = stage[2 + l];
+                all += f;
+                if (l < lane) before += f;
+            }
+            if (flag) {
+                const int k = total + before;
+                if (k >= cand_cap) stage[0] = ABAMD_MSA_BAD_GRAPH;
+                else cand[k] = c;
+            }
+            total += all;
+            ABAMD_FC_BARRIER(); /* the next chunk rewrites the flags */
+        }
+    }
+    ABAMD_FC_BARRIER();
+    status = stage[0];
+    if (status == ABAMD_MSA_OK) *n_cand_out = total < cand_cap ? total : cand_cap;
+    return status;
+}
+#undef ABAMD_HET_IN
+
+/* Launch 2 — the candidate columns as a row-major n_seq x n_cand matrix,
+ * parallel over candidates (a row's stores are adjacent across the group).
+ * n_cand is the count launch 1 reported, checked by the host against
+ * msa_len; a column index outside the matrix flags the job instead of being
+ * read. stage: 2 ints. All lanes return the same status. */
+ABAMD_FC_FN int abamd_flat_het_gather(const uint8_t *msa, int n_seq, int msa_len,
+                                      const int *cand, int n_cand, uint8_t *out,
+                                      int *stage, int lane, int n_lanes) {
+    int k, status;
+    if (lane == 0) stage[0] = ABAMD_MSA_OK;
+    ABAMD_FC_BARRIER();
+    if (n_seq <= 0 || msa_len <= 0 || n_cand < 0 || n_cand > msa_len) {
+        if (lane == 0) stage[0] = ABAMD_MSA_BAD_GRAPH;
+    } else {
+        for (k = lane; k < n_cand; k += n_lanes) {
+            const int c = cand[k];
+            int r;
             if ((unsigned)c >= (unsigned)msa_len) { stage[0] = ABAMD_MSA_BAD_GRAPH; continue; }
-            msa[(size_t)n_seq * msa_len + c] = cons_base[i];
+            for (r = 0; r < n_seq; ++r)
+                out[(size_t)r * n_cand + k] = msa[(size_t)r * msa_len + c];
         }
     }
     ABAMD_FC_BARRIER();

@@ -73,6 +73,12 @@ std::atomic<uint64_t> g_cons_device_sets{0}, g_cons_host_sets{0}, g_cons_fallbac
 std::atomic<uint64_t> g_msa_device_sets{0}, g_msa_host_sets{0}, g_msa_fallback_sets{0},
                       g_msa_d2h_bytes{0}, g_msa_kernel_ns{0};
 
+/* device multi-consensus counters (abpoa_amd_get_multicons_stats): only calls
+ * with max_n_cons > 1 under ABPOA_AMD_DEVICE_MULTICONS count */
+std::atomic<uint64_t> g_mc_device_sets{0}, g_mc_host_sets{0}, g_mc_fallback_sets{0},
+                      g_mc_one_cluster_sets{0}, g_mc_clusters{0}, g_mc_cand_cols{0},
+                      g_mc_d2h_bytes{0}, g_mc_kernel_ns{0};
+
 /* graph-fold counters (abpoa_amd_get_fold_stats): which mutation walk each
  * settled fold job ran */
 std::atomic<uint64_t> g_fold_parallel{0}, g_fold_fallback{0}, g_fold_serial{0};
@@ -265,7 +271,7 @@ struct Slot {
 struct Ctx {
     bool init = false;
     Slot slot[8];
-    DevBuf graph_slab, query_pool, ones_w, zero_ps, d_mat;
+    DevBuf graph_slab, query_pool, ones_w, zero_ps, d_mat, d_clu_masks;
     hipEvent_t ev_base;
     bool base_recorded = false;
     /* kernel-time accounting: summed event time per kernel kind, plus the
@@ -1141,6 +1147,506 @@ void device_msa(Batch &B, Slot &S, const std::vector<int> &list,
     }
 }
 
+/* Device multi-consensus (max_n_cons > 1, ABPOA_AMD_DEVICE_MULTICONS) for
+ * `list` (every set has a graph), all on slot S's stream, in chunks of sets
+ * bounded by half the arena bound of device_msa (the other half takes the
+ * compact matrices, which cannot outgrow the matrices they come from):
+ *   1. abamd_msa_rank_kernel for all sets: col[] in out_off (kept to the end
+ *      of the stage), {status, msa_len}; rank (pre_off) and scratch die here;
+ *   2. the read rows: gap-filled matrices of n_seq (+ max_n_cons with rows
+ *      and consensus rows wanted) rows in the arena, abamd_msa_place_kernel
+ *      with cons_len = -1;
+ *   3. het scan: abamd_het_count_kernel writes the candidate columns into
+ *      pre_off, abamd_het_gather_kernel the n_seq x n_cand matrices behind
+ *      the chunk's matrices — the only bulk download unless rows are wanted;
+ *   4. abamd_read_clu_from_msa per set on host threads from that matrix;
+ *   5. one-cluster sets run device_consensus (stored weights, as
+ *      heaviest_bundling does for n_clu == 1); for the others one
+ *      abamd_cons_clu_kernel launch per cluster index c over the sets with
+ *      n_clu > c, in device_consensus's workspaces (scratch, row_node_id,
+ *      row_remain, max_left, max_right — none is out_off or pre_off), each
+ *      cluster's arrays downloaded and
+ *   6. its consensus row placed (abamd_cons_row_kernel, row n_seq + c)
+ *      before the next launch overwrites them; then rows 0 .. n_seq + n_clu
+ *      - 1 come down;
+ *   7. abamd_cons_from_paths builds the result.
+ * A non-OK status anywhere drops that set's device results and returns it in
+ * `fallback`. Kernel time and bytes of rank/place/row launches and the rows
+ * are reported as the MSA share, the rest as the consensus share. */
+struct MultiConsTotals {
+    uint64_t cons_d2h = 0, msa_d2h = 0;
+    double cons_ms = 0, msa_ms = 0;
+    uint64_t one_cluster = 0, clusters = 0, cand_cols = 0;
+};
+
+struct CluWork {
+    abpoa_para_t *abpt;
+    std::vector<const uint8_t*> mat;     /* per item: n_seq x n_cand, or null */
+    std::vector<int> n_seq, n_cand, n_clu;
+    std::vector<std::vector<uint64_t>> masks;
+    std::atomic<int> next{0};
+    static void worker(void *p, int, int) {
+        CluWork &w = *(CluWork*)p;
+        for (;;) {
+            const int k = w.next.fetch_add(1);
+            if (k >= (int)w.mat.size()) break;
+            w.n_clu[k] = 1;
+            if (!w.mat[k] || w.n_cand[k] < 1) continue; /* no candidate: one cluster */
+            std::vector<uint8_t*> rows(w.n_seq[k]);
+            for (int r = 0; r < w.n_seq[k]; ++r)
+                rows[r] = const_cast<uint8_t*>(w.mat[k]) + (size_t)r * w.n_cand[k];
+            uint64_t **clu = nullptr;
+            const int n_clu = abamd_read_clu_from_msa(rows.data(), w.n_cand[k], w.n_seq[k], w.abpt, &clu);
+            w.n_clu[k] = n_clu;
+            if (n_clu > 1) {
+                const int rid_n = (w.n_seq[k] - 1) / 64 + 1;
+                w.masks[k].resize((size_t)n_clu * rid_n);
+                for (int c = 0; c < n_clu; ++c) {
+                    memcpy(&w.masks[k][(size_t)c * rid_n], clu[c], 8 * (size_t)rid_n);
+                    free(clu[c]);
+                }
+                free(clu);
+            }
+        }
+    }
+};
+
+void device_multicons(Batch &B, Slot &S, const std::vector<int> &list,
+                      std::vector<abpoa_cons_t> &cons, std::vector<int> &fallback,
+                      int n_host_threads, MultiConsTotals &T) {
+    const int n_jobs = (int)list.size();
+    if (n_jobs == 0) return;
+    Ctx &C = g_ctx;
+    abpoa_para_t *abpt = B.abpt;
+    const bool want_msa = abpt->out_msa;
+    const int cons_rows = want_msa && abpt->out_cons;
+    const int extra_rows = cons_rows ? abpt->max_n_cons : 0;
+
+    /* job arrays: two regions of d_fjobs / d_fouts, so two launches can be in
+     * flight between synchronisations; uploads go through h_stage at a
+     * running offset that restarts after every synchronisation */
+    const size_t job_sz = std::max(std::max(sizeof(abamd_msa_job_t), sizeof(abamd_het_job_t)),
+                                   std::max(sizeof(abamd_cons_clu_job_t), sizeof(abamd_cons_row_job_t)));
+    const size_t jreg = al16((size_t)n_jobs * job_sz), rreg = al16((size_t)n_jobs * 8);
+    static_assert(sizeof(abamd_msa_out_t) == 8 && sizeof(abamd_het_out_t) == 8 &&
+                  sizeof(abamd_cons_out_t) == 8, "8-byte job records");
+    S.d_fjobs.ensure(2 * jreg);
+    S.d_fouts.ensure(2 * rreg);
+    S.h_stage.ensure(2 * jreg);
+    /* These pointers stay valid across step 5a's device_consensus call on
+     * this slot, whose ensure() calls on the same three buffers must not grow
+     * (growing frees and reallocates): its list is a subset of `list`, its job
+     * (abamd_cons_job_t) is a member of abamd_cons_clu_job_t and its record is
+     * 8 bytes, so it asks for at most jreg / rreg. */
+    static_assert(sizeof(abamd_cons_job_t) <= sizeof(abamd_cons_clu_job_t), "device_consensus fits a region");
+    uint8_t *d_jobs[2] = {(uint8_t*)S.d_fjobs.p, (uint8_t*)S.d_fjobs.p + jreg};
+    uint8_t *d_recs[2] = {(uint8_t*)S.d_fouts.p, (uint8_t*)S.d_fouts.p + rreg};
+    auto upload = [&](int region, const void *src, size_t bytes) {
+        memcpy(S.h_stage.p + region * jreg, src, bytes);
+        RHIP_CHECK(hipMemcpyAsync(d_jobs[region], S.h_stage.p + region * jreg, bytes,
+                                  hipMemcpyHostToDevice, S.stream));
+    };
+    auto span_ms = [&](hipEvent_t a, hipEvent_t b) {
+        float ms = 0.f;
+        RHIP_CHECK(hipEventElapsedTime(&ms, a, b));
+        return (double)ms;
+    };
+    auto add_span = [&](hipEvent_t a, hipEvent_t b) {
+        float t1 = 0.f, t2 = 0.f;
+        RHIP_CHECK(hipEventElapsedTime(&t1, C.ev_base, a));
+        RHIP_CHECK(hipEventElapsedTime(&t2, C.ev_base, b));
+        C.spans.push_back({t1, t2});
+    };
+
+    /* ---- 1. ranks and columns for all sets ---- */
+    std::vector<abamd_msa_job_t> hj(n_jobs);
+    for (int i = 0; i < n_jobs; ++i) {
+        SetState &st = B.sets[list[i]];
+        abamd_msa_job_t &j = hj[i];
+        memset(&j, 0, sizeof(j));
+        j.g = st.g;
+        j.rank = st.pre_off;
+        j.col = st.out_off;
+        j.in_deg = st.scratch;
+        j.stack = st.scratch + st.g.node_cap;
+        j.cons_len = -1;
+        j.n_seq = st.n_seqs;
+        j.out = (abamd_msa_out_t*)d_recs[0] + i;
+    }
+    upload(0, hj.data(), (size_t)n_jobs * sizeof(abamd_msa_job_t));
+    RHIP_CHECK(hipEventRecord(S.ev1, S.stream));
+    abamd_launch_msa_rank((const abamd_msa_job_t*)d_jobs[0], n_jobs, S.stream);
+    RHIP_CHECK(hipGetLastError());
+    RHIP_CHECK(hipEventRecord(S.ev2, S.stream));
+    std::vector<abamd_msa_out_t> outs(n_jobs);
+    S.h_read.ensure(rreg);
+    RHIP_CHECK(hipMemcpyAsync(S.h_read.p, d_recs[0], (size_t)n_jobs * 8, hipMemcpyDeviceToHost, S.stream));
+    RHIP_CHECK(hipStreamSynchronize(S.stream));
+    memcpy(outs.data(), S.h_read.p, (size_t)n_jobs * 8);
+    T.msa_d2h += (size_t)n_jobs * 8;
+    T.msa_ms += span_ms(S.ev1, S.ev2);
+    add_span(S.ev1, S.ev2);
+
+    std::vector<size_t> bytes(n_jobs, 0);
+    size_t max_one = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const SetState &st = B.sets[list[i]];
+        if (outs[i].status == ABAMD_MSA_OK && outs[i].msa_len >= 1 &&
+            outs[i].msa_len <= st.g.node_n - 2 && st.n_seqs > 0) {
+            bytes[i] = al16((size_t)(st.n_seqs + extra_rows) * (size_t)outs[i].msa_len);
+            if (bytes[i] > max_one) max_one = bytes[i];
+        } else {
+            outs[i].status = ABAMD_MSA_BAD_GRAPH;
+        }
+    }
+    size_t limit = std::min(S.arena.cap, MSA_STAGE_MAX);
+    if (limit < 2 * max_one) {  /* no arena yet, or one set above the bound */
+        S.arena.ensure(2 * max_one);
+        limit = 2 * max_one;
+    }
+    const size_t half = limit / 2;
+
+    /* per-item state of one chunk */
+    struct Item {
+        int i;                   /* index into list / hj */
+        size_t moff;             /* matrix offset in the arena */
+        int msa_len, n_cand = 0, n_clu = 1, failed = 0;
+        size_t coff = 0;         /* compact matrix offset behind the matrices */
+        std::vector<uint64_t> masks;
+        std::vector<std::vector<int>> ids, cov;
+        std::vector<std::vector<uint8_t>> bases;
+        size_t mask_off = 0;     /* words into d_clu_masks */
+    };
+    std::vector<Item> items;
+    int i0 = 0;
+    while (i0 < n_jobs) {
+        size_t acc = 0;
+        int i1 = i0;
+        items.clear();
+        for (; i1 < n_jobs; ++i1) {
+            if (outs[i1].status != ABAMD_MSA_OK) { fallback.push_back(list[i1]); continue; }
+            if (acc && acc + bytes[i1] > half) break;
+            Item it;
+            it.i = i1; it.moff = acc; it.msa_len = outs[i1].msa_len;
+            items.push_back(std::move(it));
+            acc += bytes[i1];
+        }
+        i0 = i1;
+        if (items.empty()) continue;
+        const int nc = (int)items.size();
+        uint8_t *arena = (uint8_t*)S.arena.p;
+
+        /* ---- 2 + 3a. read rows, candidate columns ---- */
+        {
+            std::vector<abamd_msa_job_t> pj(nc);
+            std::vector<abamd_het_job_t> hq(nc);
+            for (int k = 0; k < nc; ++k) {
+                const Item &it = items[k];
+                SetState &st = B.sets[list[it.i]];
+                pj[k] = hj[it.i];
+                pj[k].msa = arena + it.moff;
+                pj[k].msa_len = it.msa_len;
+                pj[k].out = (abamd_msa_out_t*)d_recs[0] + k;
+                abamd_het_job_t &q = hq[k];
+                memset(&q, 0, sizeof(q));
+                q.msa = arena + it.moff;
+                q.n_seq = st.n_seqs; q.msa_len = it.msa_len; q.m = abpt->m;
+                abamd_het_depth_bounds(st.n_seqs, abpt, &q.min_het, &q.min_hom);
+                q.cand = st.pre_off; q.cand_cap = st.g.node_cap;
+                q.rec = (abamd_het_out_t*)d_recs[1] + k;
+            }
+            upload(0, pj.data(), (size_t)nc * sizeof(abamd_msa_job_t));
+            upload(1, hq.data(), (size_t)nc * sizeof(abamd_het_job_t));
+            RHIP_CHECK(hipMemsetAsync(arena, abpt->m, acc, S.stream));
+            RHIP_CHECK(hipEventRecord(S.ev0, S.stream));
+            abamd_launch_msa_place((const abamd_msa_job_t*)d_jobs[0], nc, S.stream);
+            RHIP_CHECK(hipGetLastError());
+            RHIP_CHECK(hipEventRecord(S.ev1, S.stream));
+            abamd_launch_het_count((const abamd_het_job_t*)d_jobs[1], nc, S.stream);
+            RHIP_CHECK(hipGetLastError());
+            RHIP_CHECK(hipEventRecord(S.ev2, S.stream));
+            S.h_read.ensure(2 * rreg);
+            RHIP_CHECK(hipMemcpyAsync(S.h_read.p, d_recs[0], (size_t)nc * 8, hipMemcpyDeviceToHost, S.stream));
+            RHIP_CHECK(hipMemcpyAsync(S.h_read.p + rreg, d_recs[1], (size_t)nc * 8, hipMemcpyDeviceToHost, S.stream));
+            RHIP_CHECK(hipStreamSynchronize(S.stream));
+            T.msa_d2h += (size_t)nc * 8;
+            T.cons_d2h += (size_t)nc * 8;
+            T.msa_ms += span_ms(S.ev0, S.ev1);
+            T.cons_ms += span_ms(S.ev1, S.ev2);
+            add_span(S.ev0, S.ev2);
+            const abamd_msa_out_t *po = (const abamd_msa_out_t*)S.h_read.p;
+            const abamd_het_out_t *ho = (const abamd_het_out_t*)(S.h_read.p + rreg);
+            for (int k = 0; k < nc; ++k) {
+                Item &it = items[k];
+                if (po[k].status != ABAMD_MSA_OK || ho[k].status != ABAMD_MSA_OK ||
+                    ho[k].n_cand < 0 || ho[k].n_cand > it.msa_len) it.failed = 1;
+                else it.n_cand = ho[k].n_cand;
+            }
+        }
+
+        /* ---- 3b. compact matrices: n_cand <= msa_len keeps them within `half` ---- */
+        CluWork W;
+        W.abpt = abpt;
+        W.mat.assign(nc, nullptr); W.n_seq.assign(nc, 0); W.n_cand.assign(nc, 0);
+        W.n_clu.assign(nc, 1); W.masks.resize(nc);
+        {
+            std::vector<abamd_het_job_t> gq;
+            std::vector<int> gk;
+            size_t ctot = 0;
+            for (int k = 0; k < nc; ++k) {
+                Item &it = items[k];
+                if (it.failed || it.n_cand == 0) continue;
+                SetState &st = B.sets[list[it.i]];
+                it.coff = ctot;
+                abamd_het_job_t q;
+                memset(&q, 0, sizeof(q));
+                q.msa = arena + it.moff;
+                q.n_seq = st.n_seqs; q.msa_len = it.msa_len; q.m = abpt->m;
+                q.cand = st.pre_off; q.cand_cap = st.g.node_cap;
+                q.n_cand = it.n_cand;
+                q.out = arena + acc + ctot;
+                q.rec = (abamd_het_out_t*)d_recs[1] + gq.size();
+                gq.push_back(q);
+                gk.push_back(k);
+                ctot += al16((size_t)st.n_seqs * (size_t)it.n_cand);
+            }
+            if (!gq.empty()) {
+                const int ng = (int)gq.size();
+                upload(1, gq.data(), (size_t)ng * sizeof(abamd_het_job_t));
+                RHIP_CHECK(hipEventRecord(S.ev1, S.stream));
+                abamd_launch_het_gather((const abamd_het_job_t*)d_jobs[1], ng, S.stream);
+                RHIP_CHECK(hipGetLastError());
+                RHIP_CHECK(hipEventRecord(S.ev2, S.stream));
+                S.h_read.ensure(rreg + ctot);
+                RHIP_CHECK(hipMemcpyAsync(S.h_read.p, d_recs[1], (size_t)ng * 8, hipMemcpyDeviceToHost, S.stream));
+                RHIP_CHECK(hipMemcpyAsync(S.h_read.p + rreg, arena + acc, ctot, hipMemcpyDeviceToHost, S.stream));
+                RHIP_CHECK(hipStreamSynchronize(S.stream));
+                T.cons_d2h += (size_t)ng * 8 + ctot;
+                T.cons_ms += span_ms(S.ev1, S.ev2);
+                add_span(S.ev1, S.ev2);
+                const abamd_het_out_t *go = (const abamd_het_out_t*)S.h_read.p;
+                for (int g = 0; g < ng; ++g) {
+                    Item &it = items[gk[g]];
+                    if (go[g].status != ABAMD_MSA_OK) { it.failed = 1; continue; }
+                    W.mat[gk[g]] = S.h_read.p + rreg + it.coff;
+                    W.n_seq[gk[g]] = B.sets[list[it.i]].n_seqs;
+                    W.n_cand[gk[g]] = it.n_cand;
+                }
+            }
+        }
+
+        /* ---- 4. clustering on host threads, from the compact matrices ---- */
+        abamd_pool_run(CluWork::worker, &W, n_host_threads);
+        size_t mask_words = 0;
+        int max_clu = 1;
+        for (int k = 0; k < nc; ++k) {
+            Item &it = items[k];
+            if (it.failed) continue;
+            it.n_clu = W.n_clu[k];
+            if (it.n_clu < 1 || it.n_clu > abpt->max_n_cons) { it.failed = 1; continue; }
+            if (it.n_clu > 1) {
+                it.masks.swap(W.masks[k]);
+                it.mask_off = mask_words;
+                mask_words += it.masks.size();
+                it.ids.resize(it.n_clu); it.cov.resize(it.n_clu); it.bases.resize(it.n_clu);
+                if (it.n_clu > max_clu) max_clu = it.n_clu;
+            }
+        }
+
+        /* ---- 5a. one-cluster sets: the single-consensus kernel, unchanged ---- */
+        {
+            std::vector<int> one_list, one_fb;
+            for (int k = 0; k < nc; ++k)
+                if (!items[k].failed && items[k].n_clu == 1) one_list.push_back(list[items[k].i]);
+            device_consensus(B, S, one_list, cons, one_fb, T.cons_d2h, T.cons_ms);
+            for (int s : one_fb)
+                for (int k = 0; k < nc; ++k)
+                    if (list[items[k].i] == s) items[k].failed = 1;
+        }
+
+        /* ---- 5b + 6. per cluster index: consensus, arrays down, row placed ---- */
+        if (mask_words) {
+            C.d_clu_masks.ensure(mask_words * 8);
+            S.h_stage.ensure(2 * jreg + mask_words * 8);
+            uint64_t *hm = (uint64_t*)(S.h_stage.p + 2 * jreg);
+            for (int k = 0; k < nc; ++k)
+                if (!items[k].failed && items[k].n_clu > 1)
+                    memcpy(hm + items[k].mask_off, items[k].masks.data(), 8 * items[k].masks.size());
+            RHIP_CHECK(hipMemcpyAsync(C.d_clu_masks.p, hm, mask_words * 8, hipMemcpyHostToDevice, S.stream));
+        }
+        for (int c = 0; c < max_clu; ++c) {
+            std::vector<abamd_cons_clu_job_t> cj;
+            std::vector<int> ck;
+            for (int k = 0; k < nc; ++k) {
+                Item &it = items[k];
+                if (it.failed || it.n_clu < 2 || it.n_clu <= c) continue;
+                SetState &st = B.sets[list[it.i]];
+                abamd_cons_clu_job_t j;
+                memset(&j, 0, sizeof(j));
+                j.c.g = st.g;
+                j.c.index_to_node_id = st.i2n;
+                j.c.node_id_to_index = st.n2i;
+                j.c.max_w = st.scratch;
+                j.c.best = st.scratch + st.g.node_cap;
+                j.c.score = st.row_node_id;
+                j.c.cons_id = st.row_remain;
+                j.c.cons_cov = st.max_left;
+                j.c.cons_base = (uint8_t*)st.max_right;
+                j.c.out = (abamd_cons_out_t*)d_recs[0] + cj.size();
+                j.mask = (const uint64_t*)C.d_clu_masks.p + it.mask_off + (size_t)c * st.g.rid_n;
+                cj.push_back(j);
+                ck.push_back(k);
+            }
+            std::vector<size_t> aoff(cj.size() + 1, 0);
+            std::vector<int> clen(cj.size(), 0);
+            if (!cj.empty()) {
+                const int nj = (int)cj.size();
+                upload(0, cj.data(), (size_t)nj * sizeof(abamd_cons_clu_job_t));
+                RHIP_CHECK(hipEventRecord(S.ev1, S.stream));
+                abamd_launch_cons_clu((const abamd_cons_clu_job_t*)d_jobs[0], nj, S.stream);
+                RHIP_CHECK(hipGetLastError());
+                RHIP_CHECK(hipEventRecord(S.ev2, S.stream));
+                S.h_read.ensure(rreg);
+                RHIP_CHECK(hipMemcpyAsync(S.h_read.p, d_recs[0], (size_t)nj * 8, hipMemcpyDeviceToHost, S.stream));
+                RHIP_CHECK(hipStreamSynchronize(S.stream));
+                T.cons_d2h += (size_t)nj * 8;
+                T.cons_ms += span_ms(S.ev1, S.ev2);
+                add_span(S.ev1, S.ev2);
+                const abamd_cons_out_t *co = (const abamd_cons_out_t*)S.h_read.p;
+                for (int g = 0; g < nj; ++g) {
+                    Item &it = items[ck[g]];
+                    const SetState &st = B.sets[list[it.i]];
+                    if (co[g].status != ABAMD_CONS_OK || co[g].cons_len < 0 || co[g].cons_len > st.g.node_n)
+                        it.failed = 1;
+                    else clen[g] = co[g].cons_len;
+                    aoff[g + 1] = aoff[g] + (it.failed ? 0 : al16(9 * (size_t)clen[g]));
+                }
+            }
+            /* this cluster's rows (and, at c == 0, the one-cluster sets'), then
+             * the arrays; one synchronisation for both */
+            std::vector<abamd_cons_row_job_t> rj;
+            std::vector<int> rk;
+            if (cons_rows) {
+                auto add_row = [&](int k, int len) {
+                    Item &it = items[k];
+                    SetState &st = B.sets[list[it.i]];
+                    abamd_cons_row_job_t j;
+                    memset(&j, 0, sizeof(j));
+                    j.node_n = st.g.node_n;
+                    j.col = st.out_off;
+                    j.cons_id = st.row_remain;
+                    j.cons_base = (const uint8_t*)st.max_right;
+                    j.cons_len = len;
+                    j.row = arena + it.moff + (size_t)(st.n_seqs + c) * it.msa_len;
+                    j.msa_len = it.msa_len;
+                    j.out = (abamd_msa_out_t*)d_recs[1] + rj.size();
+                    rj.push_back(j);
+                    rk.push_back(k);
+                };
+                for (size_t g = 0; g < ck.size(); ++g)
+                    if (!items[ck[g]].failed) add_row(ck[g], clen[g]);
+                if (c == 0)
+                    for (int k = 0; k < nc; ++k)
+                        if (!items[k].failed && items[k].n_clu == 1)
+                            add_row(k, cons[list[items[k].i]].cons_len[0]);
+            }
+            if (cj.empty() && rj.empty()) continue;
+            const size_t arr_bytes = aoff[cj.size()];
+            S.h_read.ensure(rreg + (arr_bytes ? arr_bytes : 1));
+            for (size_t g = 0; g < cj.size(); ++g) {
+                if (items[ck[g]].failed || !clen[g]) continue;
+                const size_t len = (size_t)clen[g];
+                uint8_t *h = S.h_read.p + rreg + aoff[g];
+                RHIP_CHECK(hipMemcpyAsync(h, cj[g].c.cons_id, 4 * len, hipMemcpyDeviceToHost, S.stream));
+                RHIP_CHECK(hipMemcpyAsync(h + 4 * len, cj[g].c.cons_cov, 4 * len, hipMemcpyDeviceToHost, S.stream));
+                RHIP_CHECK(hipMemcpyAsync(h + 8 * len, cj[g].c.cons_base, len, hipMemcpyDeviceToHost, S.stream));
+                T.cons_d2h += 9 * len;
+            }
+            if (!rj.empty()) {
+                const int nr = (int)rj.size();
+                upload(1, rj.data(), (size_t)nr * sizeof(abamd_cons_row_job_t));
+                RHIP_CHECK(hipEventRecord(S.ev1, S.stream));
+                abamd_launch_cons_row((const abamd_cons_row_job_t*)d_jobs[1], nr, S.stream);
+                RHIP_CHECK(hipGetLastError());
+                RHIP_CHECK(hipEventRecord(S.ev2, S.stream));
+                RHIP_CHECK(hipMemcpyAsync(S.h_read.p, d_recs[1], (size_t)nr * 8, hipMemcpyDeviceToHost, S.stream));
+                T.msa_d2h += (size_t)nr * 8;
+            }
+            RHIP_CHECK(hipStreamSynchronize(S.stream));
+            if (!rj.empty()) {
+                T.msa_ms += span_ms(S.ev1, S.ev2);
+                add_span(S.ev1, S.ev2);
+                const abamd_msa_out_t *ro = (const abamd_msa_out_t*)S.h_read.p;
+                for (size_t g = 0; g < rj.size(); ++g)
+                    if (ro[g].status != ABAMD_MSA_OK) items[rk[g]].failed = 1;
+            }
+            for (size_t g = 0; g < cj.size(); ++g) {
+                Item &it = items[ck[g]];
+                if (it.failed) continue;
+                const size_t len = (size_t)clen[g];
+                const uint8_t *h = S.h_read.p + rreg + aoff[g];
+                it.ids[c].assign((const int*)h, (const int*)h + len);
+                it.cov[c].assign((const int*)(h + 4 * len), (const int*)(h + 4 * len) + len);
+                it.bases[c].assign(h + 8 * len, h + 9 * len);
+            }
+        }
+
+        /* nothing of this chunk stays in flight (the mask upload, when every
+         * set that needed it has failed) */
+        RHIP_CHECK(hipStreamSynchronize(S.stream));
+
+        /* ---- 6b. rows 0 .. n_seq + n_clu - 1 ---- */
+        std::vector<size_t> roff(nc + 1, 0);
+        if (want_msa) {
+            for (int k = 0; k < nc; ++k) {
+                const Item &it = items[k];
+                const size_t rows = it.failed ? 0 : (size_t)B.sets[list[it.i]].n_seqs + (cons_rows ? it.n_clu : 0);
+                roff[k + 1] = roff[k] + al16(rows * (size_t)it.msa_len);
+            }
+            S.h_read.ensure(roff[nc] ? roff[nc] : 1);
+            for (int k = 0; k < nc; ++k) {
+                const Item &it = items[k];
+                if (it.failed) continue;
+                const size_t rows = (size_t)B.sets[list[it.i]].n_seqs + (cons_rows ? it.n_clu : 0);
+                RHIP_CHECK(hipMemcpyAsync(S.h_read.p + roff[k], arena + it.moff, rows * (size_t)it.msa_len,
+                                          hipMemcpyDeviceToHost, S.stream));
+                T.msa_d2h += rows * (size_t)it.msa_len;
+            }
+            RHIP_CHECK(hipStreamSynchronize(S.stream));
+        }
+
+        /* ---- 7. results ---- */
+        for (int k = 0; k < nc; ++k) {
+            Item &it = items[k];
+            const int s = list[it.i];
+            const int n_seq = B.sets[s].n_seqs;
+            if (it.failed) {
+                abamd_cons_clear(&cons[s]); /* a one-cluster result may exist */
+                fallback.push_back(s);
+                continue;
+            }
+            if (it.n_clu > 1) {
+                std::vector<int> lens(it.n_clu);
+                std::vector<const int*> pid(it.n_clu), pcov(it.n_clu);
+                std::vector<const uint8_t*> pb(it.n_clu);
+                for (int c = 0; c < it.n_clu; ++c) {
+                    lens[c] = (int)it.ids[c].size();
+                    pid[c] = it.ids[c].data(); pcov[c] = it.cov[c].data(); pb[c] = it.bases[c].data();
+                }
+                abamd_cons_from_paths(&cons[s], n_seq, it.n_clu, it.masks.data(), lens.data(),
+                                      pid.data(), pb.data(), pcov.data());
+            } else {
+                T.one_cluster += 1;
+            }
+            if (want_msa)
+                abamd_cons_attach_msa(&cons[s], n_seq + (cons_rows ? it.n_clu : 0), it.msa_len,
+                                      S.h_read.p + roff[k], abpt->m);
+            T.clusters += (uint64_t)it.n_clu;
+            T.cand_cols += (uint64_t)it.n_cand;
+        }
+    }
+}
+
 } // namespace
 
 /* ------------------------------------------------------------------ */
@@ -1205,6 +1711,24 @@ extern "C" void abpoa_amd_get_msa_stats(uint64_t *device_sets, uint64_t *host_se
 extern "C" void abpoa_amd_reset_msa_stats(void) {
     g_msa_device_sets = 0; g_msa_host_sets = 0; g_msa_fallback_sets = 0;
     g_msa_d2h_bytes = 0; g_msa_kernel_ns = 0;
+}
+
+extern "C" void abpoa_amd_get_multicons_stats(uint64_t *device_sets, uint64_t *host_sets,
+        uint64_t *fallback_sets, uint64_t *one_cluster_sets, uint64_t *clusters,
+        uint64_t *cand_cols, uint64_t *d2h_bytes, uint64_t *kernel_ns) {
+    if (device_sets) *device_sets = g_mc_device_sets.load();
+    if (host_sets) *host_sets = g_mc_host_sets.load();
+    if (fallback_sets) *fallback_sets = g_mc_fallback_sets.load();
+    if (one_cluster_sets) *one_cluster_sets = g_mc_one_cluster_sets.load();
+    if (clusters) *clusters = g_mc_clusters.load();
+    if (cand_cols) *cand_cols = g_mc_cand_cols.load();
+    if (d2h_bytes) *d2h_bytes = g_mc_d2h_bytes.load();
+    if (kernel_ns) *kernel_ns = g_mc_kernel_ns.load();
+}
+extern "C" void abpoa_amd_reset_multicons_stats(void) {
+    g_mc_device_sets = 0; g_mc_host_sets = 0; g_mc_fallback_sets = 0;
+    g_mc_one_cluster_sets = 0; g_mc_clusters = 0; g_mc_cand_cols = 0;
+    g_mc_d2h_bytes = 0; g_mc_kernel_ns = 0;
 }
 
 extern "C" void abpoa_amd_get_fold_stats(uint64_t *parallel_folds, uint64_t *fallback_folds,
@@ -1576,9 +2100,18 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     const bool dev_cons = abpt->cons_algrm == ABPOA_HB && abpt->max_n_cons == 1 &&
                           !getenv("ABPOA_AMD_HOST_CONS") &&
                           !(want_msa && (getenv("ABPOA_AMD_HOST_MSA") || !abpt->use_read_ids));
+    /* multi-consensus on the device, behind its switch (read once per call):
+     * heaviest bundle over read-id bitsets, an alphabet whose symbol depths
+     * the het scan keeps in registers, and no host-path override */
+    const char *mc_env = getenv("ABPOA_AMD_DEVICE_MULTICONS");
+    const bool mc_on = mc_env && *mc_env && *mc_env != '0' && abpt->max_n_cons > 1;
+    const bool dev_multi = mc_on && abpt->cons_algrm == ABPOA_HB && abpt->use_read_ids &&
+                           !abpt->use_qv && abpt->m <= ABAMD_HET_MAX_M &&
+                           !getenv("ABPOA_AMD_HOST_CONS") &&
+                           !(want_msa && getenv("ABPOA_AMD_HOST_MSA"));
     std::vector<int> dev_list, host_list, fallback;
     for (int s = 0; s < n_sets; ++s) {
-        if (dev_cons && B.sets[s].g.node_n > 2) dev_list.push_back(s);
+        if ((dev_cons || dev_multi) && B.sets[s].g.node_n > 2) dev_list.push_back(s);
         else host_list.push_back(s);
     }
     std::vector<abpoa_cons_t> dcons(n_sets);
@@ -1586,10 +2119,21 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     std::vector<char> from_device(n_sets, 0);
     uint64_t cons_d2h = 0;
     double cons_kernel_ms = 0;
-    device_consensus(B, S0, dev_list, dcons, fallback, cons_d2h, cons_kernel_ms);
     uint64_t msa_d2h = 0;
     double msa_kernel_ms = 0;
-    if (want_msa && !dev_list.empty()) {
+    MultiConsTotals mct;
+    if (dev_multi) {
+        device_multicons(B, S0, dev_list, dcons, fallback, n_host_threads, mct);
+        cons_d2h += mct.cons_d2h;
+        cons_kernel_ms += mct.cons_ms;
+        /* the rows are a by-product here: without out_msa their launches are
+         * part of the consensus stage's cost */
+        if (want_msa) { msa_d2h += mct.msa_d2h; msa_kernel_ms += mct.msa_ms; }
+        else { cons_d2h += mct.msa_d2h; cons_kernel_ms += mct.msa_ms; }
+    } else {
+        device_consensus(B, S0, dev_list, dcons, fallback, cons_d2h, cons_kernel_ms);
+    }
+    if (want_msa && !dev_multi && !dev_list.empty()) {
         /* same stream, after the consensus kernel; a set that fails here
          * gives up its device consensus too and joins the fallback list */
         std::vector<char> cons_failed(n_sets, 0);
@@ -1617,6 +2161,16 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
     g_cons_fallback_sets += n_fallback;
     g_cons_d2h_bytes += cons_d2h;
     g_cons_kernel_ns += (uint64_t)(cons_kernel_ms * 1e6);
+    if (mc_on) {
+        g_mc_device_sets += n_dev;
+        g_mc_host_sets += n_host;
+        g_mc_fallback_sets += n_fallback;
+        g_mc_one_cluster_sets += mct.one_cluster;
+        g_mc_clusters += mct.clusters;
+        g_mc_cand_cols += mct.cand_cols;
+        g_mc_d2h_bytes += mct.cons_d2h + mct.msa_d2h + hc.d2h_bytes;
+        g_mc_kernel_ns += (uint64_t)((mct.cons_ms + mct.msa_ms) * 1e6);
+    }
     if (want_msa) {
         /* the host path's rows cost the graph download (shared with the
          * consensus, reported in both sets of counters) */
@@ -1658,6 +2212,13 @@ extern "C" int abpoa_amd_msa_batch_resident(abpoa_para_t *abpt, int n_sets, cons
                     msa_kernel_ms, (unsigned long long)msa_d2h,
                     (unsigned long long)n_dev, (unsigned long long)n_host,
                     (unsigned long long)n_fallback);
+        if (mc_on)
+            fprintf(stderr, "[abamd timing resident] multicons %s: one-cluster sets %llu clusters %llu "
+                            "candidate columns %llu kernels %.2fms d2h %llu B\n",
+                    dev_multi ? "device" : "host (ineligible)",
+                    (unsigned long long)mct.one_cluster, (unsigned long long)mct.clusters,
+                    (unsigned long long)mct.cand_cols, mct.cons_ms + mct.msa_ms,
+                    (unsigned long long)(mct.cons_d2h + mct.msa_d2h + hc.d2h_bytes));
         fprintf(stderr, "[abamd timing resident] hipMalloc %ld calls %.2fs\n",
                 g_alloc_n, g_alloc_s);
     }

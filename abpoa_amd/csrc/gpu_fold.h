@@ -124,6 +124,53 @@ typedef struct {
 void abamd_launch_msa_rank(const abamd_msa_job_t *dev_jobs, int n_jobs, void *stream);
 void abamd_launch_msa_place(const abamd_msa_job_t *dev_jobs, int n_jobs, void *stream);
 
+/* ---- device multi-consensus (gpu_fold.hip :: abamd_het_count_kernel,
+ * abamd_het_gather_kernel, abamd_cons_clu_kernel, abamd_cons_row_kernel) ----
+ * After abamd_msa_rank_kernel and abamd_msa_place_kernel (cons_len < 0) have
+ * built a set's read rows: the het scan finds the candidate heterozygous
+ * columns (launch 1 writes their indices to cand[] and {status, n_cand};
+ * launch 2 gathers them into the row-major n_seq x n_cand matrix the host
+ * clustering reads), then one abamd_cons_clu_kernel launch per cluster index
+ * runs the heaviest-bundle pass with that cluster's read mask, and
+ * abamd_cons_row_kernel places the cluster's consensus row. The graph pools,
+ * i2n, n2i, col[] and the read rows are only read. */
+typedef struct {
+    int32_t status;              /* ABAMD_MSA_* */
+    int32_t n_cand;
+} abamd_het_out_t;
+
+typedef struct {
+    const uint8_t *msa;          /* n_seq x msa_len read rows */
+    int n_seq, msa_len, m;
+    int min_het, min_hom;        /* depth window (abamd_het_depth_bounds) */
+    int *cand; int cand_cap;     /* candidate column indices, ascending */
+    int n_cand;                  /* gather only: launch 1's count */
+    uint8_t *out;                /* gather only: n_seq x n_cand */
+    abamd_het_out_t *rec;
+} abamd_het_job_t;
+
+void abamd_launch_het_count(const abamd_het_job_t *dev_jobs, int n_jobs, void *stream);
+void abamd_launch_het_gather(const abamd_het_job_t *dev_jobs, int n_jobs, void *stream);
+
+typedef struct {
+    abamd_cons_job_t c;          /* as for abamd_cons_kernel */
+    const uint64_t *mask;        /* the cluster's read ids, c.g.rid_n words */
+} abamd_cons_clu_job_t;
+
+void abamd_launch_cons_clu(const abamd_cons_clu_job_t *dev_jobs, int n_jobs, void *stream);
+
+typedef struct {
+    int node_n;
+    const int *col;              /* abamd_msa_rank_kernel's columns */
+    const int *cons_id;          /* consensus kernel outputs */
+    const uint8_t *cons_base;
+    int cons_len;
+    uint8_t *row; int msa_len;   /* the gap-filled consensus row */
+    abamd_msa_out_t *out;        /* status only; msa_len is left alone */
+} abamd_cons_row_job_t;
+
+void abamd_launch_cons_row(const abamd_cons_row_job_t *dev_jobs, int n_jobs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -687,6 +687,109 @@ extern "C" void abamd_launch_msa_place(const abamd_msa_job_t *dev_jobs, int n_jo
                        (hipStream_t)stream, dev_jobs, n_jobs);
 }
 
+/* ------------------------------------------------------------------ */
+/* Device multi-consensus kernels.                                     */
+/* ------------------------------------------------------------------ */
+
+/* One 64-lane workgroup per set throughout, like the kernels above; every
+ * body is the shared text of abamd_msa_core.inc / abamd_cons_core.inc that
+ * the host twin (tests/test_multicons_twin) runs with one lane. None of them
+ * aborts or loops without a bound: a failed check sets the job's status and
+ * the host sends that set alone to the graph download.
+ *
+ * Het scan, launch 1: per-column symbol depths over the read rows (lanes on
+ * adjacent columns, six scalar counters), candidate flags, ascending
+ * candidate list through a per-64-column prefix in LDS; record {status,
+ * n_cand}. LDS: ABAMD_HET_STAGE ints. */
+extern "C" __global__ __launch_bounds__(FOLD_WAVE)
+void abamd_het_count_kernel(const abamd_het_job_t *jobs, int n_jobs) {
+    __shared__ int stage[ABAMD_HET_STAGE];
+    const int j = blockIdx.x;
+    if (j >= n_jobs) return;
+    const abamd_het_job_t *job = &jobs[j];
+    int n_cand = 0;
+    const int status = abamd_flat_het_count(job->msa, job->n_seq, job->msa_len, job->m,
+                                            job->min_het, job->min_hom, job->cand,
+                                            job->cand_cap, stage, &n_cand,
+                                            (int)threadIdx.x, FOLD_WAVE);
+    if (threadIdx.x == 0) {
+        job->rec->status = status;
+        job->rec->n_cand = n_cand;
+    }
+}
+
+/* Het scan, launch 2: the candidate columns as the compact matrix the host
+ * clustering reads; overwrites rec->status. LDS: 2 ints. */
+extern "C" __global__ __launch_bounds__(FOLD_WAVE)
+void abamd_het_gather_kernel(const abamd_het_job_t *jobs, int n_jobs) {
+    __shared__ int stage[2];
+    const int j = blockIdx.x;
+    if (j >= n_jobs) return;
+    const abamd_het_job_t *job = &jobs[j];
+    const int status = abamd_flat_het_gather(job->msa, job->n_seq, job->msa_len, job->cand,
+                                             job->n_cand, job->out, stage,
+                                             (int)threadIdx.x, FOLD_WAVE);
+    if (threadIdx.x == 0) job->rec->status = status;
+}
+
+/* One cluster's heaviest-bundle pass: abamd_cons_kernel's frame around
+ * abamd_flat_cons_phased_clu (edge weight = the cluster's reads on the edge,
+ * coverage = the same over the node's out-edges). LDS: 3 x 64 ints. */
+extern "C" __global__ __launch_bounds__(FOLD_WAVE)
+void abamd_cons_clu_kernel(const abamd_cons_clu_job_t *jobs, int n_jobs) {
+    __shared__ int stage[3 * ABAMD_CONS_CHUNK];
+    const int j = blockIdx.x;
+    if (j >= n_jobs) return;
+    const abamd_cons_job_t *job = &jobs[j].c;
+    const flat_graph_t gl = job->g; /* by value: pool pointers in registers */
+    int cons_len = 0;
+    const int status = abamd_flat_cons_phased_clu(&gl, jobs[j].mask, job->index_to_node_id,
+                                                  job->node_id_to_index,
+                                                  job->max_w, job->best, job->score,
+                                                  job->cons_id /* row path */, job->cons_id,
+                                                  job->cons_base, job->cons_cov,
+                                                  stage, &cons_len, (int)threadIdx.x, FOLD_WAVE);
+    if (threadIdx.x == 0) {
+        job->out->status = status;
+        job->out->cons_len = cons_len;
+    }
+}
+
+/* One consensus row from the ids and bases a consensus kernel left in the
+ * slab, bounds-checked like abamd_msa_place_kernel's. LDS: 2 ints. */
+extern "C" __global__ __launch_bounds__(FOLD_WAVE)
+void abamd_cons_row_kernel(const abamd_cons_row_job_t *jobs, int n_jobs) {
+    __shared__ int stage[2];
+    const int j = blockIdx.x;
+    if (j >= n_jobs) return;
+    const abamd_cons_row_job_t *job = &jobs[j];
+    const int status = abamd_flat_msa_place_cons_row(job->node_n, job->col, job->msa_len,
+                                                     job->row, job->cons_id, job->cons_base,
+                                                     job->cons_len, stage,
+                                                     (int)threadIdx.x, FOLD_WAVE);
+    if (threadIdx.x == 0) job->out->status = status;
+}
+
+extern "C" void abamd_launch_het_count(const abamd_het_job_t *dev_jobs, int n_jobs, void *stream) {
+    hipLaunchKernelGGL(abamd_het_count_kernel, dim3(n_jobs), dim3(FOLD_WAVE), 0,
+                       (hipStream_t)stream, dev_jobs, n_jobs);
+}
+
+extern "C" void abamd_launch_het_gather(const abamd_het_job_t *dev_jobs, int n_jobs, void *stream) {
+    hipLaunchKernelGGL(abamd_het_gather_kernel, dim3(n_jobs), dim3(FOLD_WAVE), 0,
+                       (hipStream_t)stream, dev_jobs, n_jobs);
+}
+
+extern "C" void abamd_launch_cons_clu(const abamd_cons_clu_job_t *dev_jobs, int n_jobs, void *stream) {
+    hipLaunchKernelGGL(abamd_cons_clu_kernel, dim3(n_jobs), dim3(FOLD_WAVE), 0,
+                       (hipStream_t)stream, dev_jobs, n_jobs);
+}
+
+extern "C" void abamd_launch_cons_row(const abamd_cons_row_job_t *dev_jobs, int n_jobs, void *stream) {
+    hipLaunchKernelGGL(abamd_cons_row_kernel, dim3(n_jobs), dim3(FOLD_WAVE), 0,
+                       (hipStream_t)stream, dev_jobs, n_jobs);
+}
+
 extern "C" void abamd_launch_fold_round(const abamd_fold_round_job_t *dev_jobs,
                                         int n_jobs, void *stream) {
     hipLaunchKernelGGL(abamd_fold_round_kernel, dim3(n_jobs), dim3(64), 0,

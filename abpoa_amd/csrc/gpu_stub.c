@@ -58,6 +58,21 @@ void abpoa_amd_get_msa_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_
     if (kernel_ns) *kernel_ns = 0;
 }
 void abpoa_amd_reset_msa_stats(void) {}
+/* nor a device multi-consensus */
+void abpoa_amd_get_multicons_stats(uint64_t *device_sets, uint64_t *host_sets,
+                                   uint64_t *fallback_sets, uint64_t *one_cluster_sets,
+                                   uint64_t *clusters, uint64_t *cand_cols,
+                                   uint64_t *d2h_bytes, uint64_t *kernel_ns) {
+    if (device_sets) *device_sets = 0;
+    if (host_sets) *host_sets = 0;
+    if (fallback_sets) *fallback_sets = 0;
+    if (one_cluster_sets) *one_cluster_sets = 0;
+    if (clusters) *clusters = 0;
+    if (cand_cols) *cand_cols = 0;
+    if (d2h_bytes) *d2h_bytes = 0;
+    if (kernel_ns) *kernel_ns = 0;
+}
+void abpoa_amd_reset_multicons_stats(void) {}
 /* nor a device fold */
 void abpoa_amd_get_fold_stats(uint64_t *parallel_folds, uint64_t *fallback_folds,
                               uint64_t *serial_folds) {

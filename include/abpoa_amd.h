@@ -280,6 +280,37 @@ void abpoa_amd_get_msa_stats(uint64_t *device_sets, uint64_t *host_sets, uint64_
                              uint64_t *d2h_bytes, uint64_t *kernel_ns);
 void abpoa_amd_reset_msa_stats(void);
 
+/* Multi-consensus (abpt->max_n_cons > 1) stage of the batched device-resident
+ * driver. By default such calls download every set's graph for the host
+ * clustering and consensus. With the environment variable
+ * ABPOA_AMD_DEVICE_MULTICONS set (to anything not starting with '0'; read on
+ * every batch call) the stage runs on the device for heaviest-bundle calls
+ * with read-id tracking and an alphabet of at most 5 symbols, unless
+ * ABPOA_AMD_HOST_CONS (or, with out_msa, ABPOA_AMD_HOST_MSA) is set: the read
+ * rows of the row-column matrix are built there, a scan finds the candidate
+ * heterozygous columns, only those columns come down for the host k-medoids
+ * clustering, and one consensus pass per cluster runs on the device with
+ * cluster-filtered edge weights. Outputs are identical on both paths. Sets
+ * served there also count as device_sets of the consensus counters and, with
+ * out_msa, of the MSA counters.
+ *
+ * Counters are cumulative since the last reset and count only calls with
+ * max_n_cons > 1 made while the variable is set:
+ *   device_sets       sets whose clusters and consensus came from the device stage
+ *   host_sets         sets that took the graph-download path, for any reason
+ *   fallback_sets     the subset of host_sets caused by a non-OK device status
+ *   one_cluster_sets  device sets the clustering left in one cluster
+ *   clusters          consensus sequences emitted for device sets
+ *   cand_cols         candidate columns downloaded for device sets
+ *   d2h_bytes         bytes the whole stage copied device-to-host
+ *   kernel_ns         kernel time of the stage's launches (HIP events)
+ * Any pointer may be NULL. Builds without the GPU core report zeros. */
+void abpoa_amd_get_multicons_stats(uint64_t *device_sets, uint64_t *host_sets,
+                                   uint64_t *fallback_sets, uint64_t *one_cluster_sets,
+                                   uint64_t *clusters, uint64_t *cand_cols,
+                                   uint64_t *d2h_bytes, uint64_t *kernel_ns);
+void abpoa_amd_reset_multicons_stats(void);
+
 /* Graph-fold stage of the batched device-resident driver. Each read of each
  * set is folded into the set's graph by one fold kernel job; the graph
  * mutation walk inside it runs across the job's 64 lanes (abamd_fold_par.inc).
