@@ -26,10 +26,7 @@
 #include "abpoa_amd.h"
 #include "gpu_core.h"
 #include "abamd_util.h"
-
-#define HIP_CHECK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { \
-    fprintf(stderr, "[abpoa_amd] HIP error %s at %s:%d: %s\n", hipGetErrorName(_e), __FILE__, __LINE__, hipGetErrorString(_e)); \
-    exit(EXIT_FAILURE); } } while (0)
+#include "gpu_host.h"
 
 static std::atomic<uint64_t> g_dp_cells{0}, g_kernel_ns{0}, g_launches{0}, g_alg_bytes{0};
 static std::atomic<uint64_t> g_pack_ns{0}, g_stage_ns{0}, g_gpu_ns{0}, g_unpack_ns{0};
@@ -124,19 +121,6 @@ struct HostBuf {
         return off;
     }
     uint8_t *at(size_t off) { return v.data() + off; }
-};
-
-struct PinnedBuf {
-    uint8_t *p = nullptr;
-    size_t cap = 0;
-    void ensure(size_t n) {
-        if (n <= cap) return;
-        size_t want = cap ? cap : 1 << 20;
-        while (want < n) want <<= 1;
-        if (p) HIP_CHECK(hipHostFree(p));
-        HIP_CHECK(hipHostMalloc((void**)&p, want));
-        cap = want;
-    }
 };
 
 /* Per-slot device context: slots 0/1 are the two pipeline groups, slot 2 the
@@ -358,33 +342,33 @@ struct BatchJob {
     int64_t *cells_out;      /* optional: actual banded cells written back */
 };
 
-/* score-width pick (abpoa_align_simd.c:1284-1302); assumes uniform paras */
-static void pick_width(abpoa_para_t *abpt, int qlen, int gn, int *bits, int *inf_min) {
+} // namespace
+
+/* out-of-band score floor at `bits` (16 or 32): the type's minimum lifted by
+ * the largest single penalty, plus 512 extensions of headroom
+ * (abpoa_align_simd.c:1284-1302) */
+extern "C" int abamd_inf_min(const abpoa_para_t *abpt, int bits) {
+    const int32_t lo = bits == 16 ? INT16_MIN : INT32_MIN;
+    int32_t gap_oe1 = abpt->gap_open1 + abpt->gap_ext1;
+    int32_t gap_oe2 = abpt->gap_open2 + abpt->gap_ext2;
+    int32_t ext_max = abpt->gap_ext1 > abpt->gap_ext2 ? abpt->gap_ext1 : abpt->gap_ext2;
+    int32_t im = lo + abpt->min_mis;
+    if (lo + gap_oe1 > im) im = lo + gap_oe1;
+    if (lo + gap_oe2 > im) im = lo + gap_oe2;
+    return im + 512 * ext_max;
+}
+
+/* score-width pick (abpoa_align_simd.c:1284-1302); assumes uniform paras.
+ * Shared with the device-resident batch driver. */
+extern "C" void abamd_pick_width(abpoa_para_t *abpt, int qlen, int gn, int *bits, int *inf_min) {
     int32_t gap_oe1 = abpt->gap_open1 + abpt->gap_ext1;
     int32_t gap_oe2 = abpt->gap_open2 + abpt->gap_ext2;
     int len = qlen > gn ? qlen : gn;
     int32_t max_score = (int32_t)qlen * abpt->max_mat;
     int32_t alt = (int32_t)len * abpt->gap_ext1 + abpt->gap_open1;
     if (alt > max_score) max_score = alt;
-    int32_t ext_max = abpt->gap_ext1 > abpt->gap_ext2 ? abpt->gap_ext1 : abpt->gap_ext2;
-    if (max_score <= INT16_MAX - abpt->min_mis - gap_oe1 - gap_oe2) {
-        int32_t im = INT16_MIN + abpt->min_mis;
-        if (INT16_MIN + gap_oe1 > im) im = INT16_MIN + gap_oe1;
-        if (INT16_MIN + gap_oe2 > im) im = INT16_MIN + gap_oe2;
-        *inf_min = im + 512 * ext_max; *bits = 16;
-    } else {
-        int32_t im = INT32_MIN + abpt->min_mis;
-        if (INT32_MIN + gap_oe1 > im) im = INT32_MIN + gap_oe1;
-        if (INT32_MIN + gap_oe2 > im) im = INT32_MIN + gap_oe2;
-        *inf_min = im + 512 * ext_max; *bits = 32;
-    }
-}
-
-} // namespace
-
-/* score-width pick, shared with the device-resident batch driver */
-extern "C" void abamd_pick_width(abpoa_para_t *abpt, int qlen, int gn, int *bits, int *inf_min) {
-    pick_width(abpt, qlen, gn, bits, inf_min);
+    *bits = max_score <= INT16_MAX - abpt->min_mis - gap_oe1 - gap_oe2 ? 16 : 32;
+    *inf_min = abamd_inf_min(abpt, *bits);
 }
 
 /* int16 with a large gap extension lifts inf_min (INT16_MIN + penalties +
@@ -499,7 +483,7 @@ static int prepare_internal(BatchJob *batch, int n_jobs, int slot, const int64_t
                 if (c.min_est && c.min_est[i] > (*c.arena_est)[i]) (*c.arena_est)[i] = c.min_est[i];
                 int inf_min;
                 int span = B.ab->abg->node_id_to_index[B.end_node_id] - B.ab->abg->node_id_to_index[B.beg_node_id] + 1;
-                pick_width(B.abpt, B.qlen, span, &(*c.bits_v)[i], &inf_min);
+                abamd_pick_width(B.abpt, B.qlen, span, &(*c.bits_v)[i], &inf_min);
                 (*c.packs)[i].jb.inf_min = inf_min;
                 (*c.packs)[i].cigar_off = 0;
             }
@@ -551,18 +535,7 @@ static int prepare_internal(BatchJob *batch, int n_jobs, int slot, const int64_t
     int bits = bits_max;
     if (bits == 32) {
         /* recompute inf_min at 32-bit for every job */
-        for (int i = 0; i < n_jobs; ++i) {
-            int b2, im;
-            BatchJob &B = batch[i];
-            int span = B.ab->abg->node_id_to_index[B.end_node_id] - B.ab->abg->node_id_to_index[B.beg_node_id] + 1;
-            (void)span; (void)b2;
-            int32_t gap_oe1 = abpt->gap_open1 + abpt->gap_ext1, gap_oe2 = abpt->gap_open2 + abpt->gap_ext2;
-            int32_t ext_max = abpt->gap_ext1 > abpt->gap_ext2 ? abpt->gap_ext1 : abpt->gap_ext2;
-            im = INT32_MIN + abpt->min_mis;
-            if (INT32_MIN + gap_oe1 > im) im = INT32_MIN + gap_oe1;
-            if (INT32_MIN + gap_oe2 > im) im = INT32_MIN + gap_oe2;
-            packs[i].jb.inf_min = im + 512 * ext_max;
-        }
+        for (int i = 0; i < n_jobs; ++i) packs[i].jb.inf_min = abamd_inf_min(abpt, 32);
     }
     PendingBatch &PB = g_slots[slot];
     PB.batch = batch;
